@@ -17,6 +17,12 @@ Inputs are resident in HBM before timing: uint8 frames (uniform random pixels) a
 5-person overlays (synthetic weights carry no meaning, so a deterministic people field is added to
 the net output -- its cost is counted).
 
+A plain run sets up, warms up, times --steps steps and prints one JSON line (`value`: frames/s,
+`ms_per_step`: one timed step); --dump-outputs DIR then also writes what the last timed step
+returned.  --full adds, after the timed steps, everything beside the headline figure: the CPU
+baseline and keypoint parity, the measured ceilings, the post-processing roofline's own batches, and
+the split-precision, config-4 and config-5 legs in child processes.
+
 Multi-GPU (--gpus N): one process per GPU.  Started under torch.distributed.run the ranks come
 from the environment; started directly, this process spawns N ranks (openpose_amd.parallel.
 launch_ranks) before any GPU call and waits for them.  Frames shard across ranks with no
@@ -63,7 +69,18 @@ def parse():
                     help="body25: BASELINE configs[1]/[2]; multiscale: configs[3] (4 scales); "
                          "body135: configs[4] (BODY_135 net-output injection, 20 people)")
     ap.add_argument("--people", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the "
+                         "CPU baseline and keypoint parity, the split-precision / config-4 / config-5 "
+                         "legs, the measured ceilings and the post-processing roofline's own "
+                         "batches.  Off: set up, warm up, time the steps, print the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0: after the timed steps write what the last timed step returned "
+                         "(every frame's keypoints and scores, a fixed sample of the net output) as "
+                         "DIR/<name>.npy, float32; the inputs are seeded, so two builds run with "
+                         "the same arguments can be compared array for array")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline and parity legs")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU-baseline threads; 0: the CPUs this process may run on "
                          "(sched_getaffinity), capped by OMP_NUM_THREADS when the host sets it")
@@ -81,7 +98,7 @@ def parse():
                     help="steps per gather of the per-frame records to rank 0 (N > 1); 0: one gather "
                          "at the end of the timed steps, so ranks are coupled only there")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="the default run (1 GPU, body25, fp16) also times split precision, "
+                    help="a --full run (1 GPU, body25, fp16) also times split precision, "
                          "config 4 (multiscale) and config 5 (body135) in child processes and "
                          "reports them under `configs`; this flag skips those legs")
     ap.add_argument("--dev", action="append", default=[], metavar="KEY=VAL",
@@ -185,6 +202,33 @@ def dump_records(path, ordered):
     kp = np.concatenate([np.asarray(k, np.float32).reshape(-1) for k, _ in ordered] + [np.zeros(0, np.float32)])
     ks = np.concatenate([np.asarray(s, np.float32).reshape(-1) for _, s in ordered] + [np.zeros(0, np.float32)])
     np.savez(path, counts=counts, keypoints=kp, scores=ks)
+
+
+DUMP_NET_FRAMES = 16   # frames of the net output --dump-outputs keeps (1.2 MB each at config 2)
+
+
+def dump_outputs(path, pose, frames, max_people, net=None):
+    """--dump-outputs: what the last collected batch returned to its caller, as float32 .npy files
+    of fixed shapes -- people.npy [frames] (people found per frame), keypoints.npy [frames,
+    max_people, parts, 3] and scores.npy [frames, max_people] (rows past a frame's people are 0)
+    -- and, with a net, net_output.npy: DUMP_NET_FRAMES evenly spaced frames of the batch's net
+    output (the last scale's; the people overlay already added in place), and their indices in
+    net_output_frames.npy."""
+    os.makedirs(path, exist_ok=True)
+    kp = np.zeros((frames, max_people, pose.parts, 3), np.float32)
+    ks = np.zeros((frames, max_people), np.float32)
+    people = np.zeros(frames, np.float32)
+    for f in range(frames):
+        k, s = pose.keypoints(f)
+        assert len(k) <= max_people, (f, len(k), max_people)
+        kp[f, :len(k)], ks[f, :len(s)], people[f] = k, s, len(k)
+    np.save(os.path.join(path, "people.npy"), people)
+    np.save(os.path.join(path, "keypoints.npy"), kp)
+    np.save(os.path.join(path, "scores.npy"), ks)
+    if net is not None:
+        pick = np.unique(np.linspace(0, frames - 1, min(frames, DUMP_NET_FRAMES)).astype(np.int64))
+        np.save(os.path.join(path, "net_output.npy"), net.output_numpy()[pick])
+        np.save(os.path.join(path, "net_output_frames.npy"), pick.astype(np.float32))
 
 
 def tile_aligned_batch(cus, rounds=4):
@@ -568,7 +612,8 @@ def extra_legs(args, timeout=240):
     env = {k: v for k, v in os.environ.items() if k not in _TORCHRUN_ENV}
     out = {}
     for name, extra in EXTRA_LEGS:
-        cmd = [sys.executable, "-u", os.path.abspath(__file__), "--gpus", "1", "--no-cpu-baseline",
+        # (--full: each leg's summary carries its measured ceilings and post-processing roofline)
+        cmd = [sys.executable, "-u", os.path.abspath(__file__), "--gpus", "1", "--full", "--no-cpu-baseline",
                "--no-extra-configs"] + extra + sum((["--dev", d] for d in args.dev), [])
         t0 = time.perf_counter()
         try:
@@ -637,9 +682,11 @@ def rank_main(args, rank, world, local):
     assert net_sizes[0] == (NET_W, NET_H)
     flops_frame = sum(net.flops_per_frame(h, w) for (w, h) in net_sizes)
 
-    # net-output statistics before any overlay (the overlay is added in place into it)
-    pose.forward_frames(frames[first_content])
-    out_std = float(net.output_numpy()[:2].std()) if nscales == 1 else None
+    # --full: net-output statistics before any overlay (the overlay is added in place into it)
+    out_std = None
+    if args.full:
+        pose.forward_frames(frames[first_content])
+        out_std = float(net.output_numpy()[:2].std()) if nscales == 1 else None
     # the people field of a frame depends on its global frame id, like its pixels: frame id
     # k * B + f of global batch k (content c = k % CONTENTS) gets overlay seed c * B + f (= the
     # frame id modulo the contents' period), so every step's post-processing sees new fields
@@ -720,23 +767,26 @@ def rank_main(args, rank, world, local):
     assert nfw in (args.steps, args.steps * nscales), nfw
     assert npost == args.steps, npost
     net_ms = fw_ms / args.steps            # all scales of one step
-    post_ms /= npost
+    if rank == 0 and args.dump_outputs:   # the last timed step's batch is the last one collected
+        dump_outputs(args.dump_outputs, pose, B, 4 * args.people + 8, net)
     # In the timed loop batch i's post-processing runs beside batch i+1's nets (alternating net
     # outputs, PoseHip::next_output), so its event span there includes time-sharing with them.
     # Its own time, the post_roofline's denominator, comes from three more untimed batches in the
-    # single-buffer order (each batch's nets wait for the previous post-processing).
-    post_overlap_ms = post_ms
-    with dev_switches(NET_OUT_ALT=0):
-        pose.set_timing(True)
-        for i in range(3):
-            step(i, False)
-        drain(False)
-        npost_s, post_s_ms = pose.read_timing()
-        pose.set_timing(False)
-    post_ms = post_s_ms / npost_s
-    per_rank = [[rank, elapsed, net_ms, post_ms]]
+    # single-buffer order (each batch's nets wait for the previous post-processing): --full only.
+    post_overlap_ms = post_ms / npost
+    post_ms = -1.0   # (not measured: reported as null)
+    if args.full:
+        with dev_switches(NET_OUT_ALT=0):
+            pose.set_timing(True)
+            for i in range(3):
+                step(i, False)
+            drain(False)
+            npost_s, post_s_ms = pose.read_timing()
+            pose.set_timing(False)
+        post_ms = post_s_ms / npost_s
+    per_rank = [[rank, elapsed, net_ms, post_ms, post_overlap_ms]]
     if dist is not None:
-        t = torch.tensor([rank, elapsed, net_ms, post_ms], device=comm_dev, dtype=torch.float64)
+        t = torch.tensor(per_rank[0], device=comm_dev, dtype=torch.float64)
         allr = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(allr, t)
         per_rank = [x.tolist() for x in allr]
@@ -744,9 +794,10 @@ def rank_main(args, rank, world, local):
         net_ms = max(r[2] for r in per_rank)
         post_ms = max(r[3] for r in per_rank)
 
-    # measured ceilings of this GPU (outside the timed region): the rate the conv instruction
-    # reaches from registers on random operands is the attainable MFMA roof under this clock
-    peaks = ctx.probe_peaks()
+    # --full: measured ceilings of this GPU (outside the timed region): the rate the conv
+    # instruction reaches from registers on random operands is the attainable MFMA roof under
+    # this clock
+    peaks = ctx.probe_peaks() if args.full else None
 
     host_ms = host_breakdown(host, args.steps, collect_times)
     rank_hosts = rank_host_info(dist, host_ms)
@@ -796,8 +847,10 @@ def rank_main(args, rank, world, local):
             "frames_gathered_in_order": total_frames,
             "gather_interval_steps": args.gather_interval or "at the end of the timed steps",
         },
+        # post_ms_per_step: the post-processing alone (--full: its own single-buffer batches)
         "per_rank": [{"rank": int(r[0]), "s": round(r[1], 4), "cnn_ms_per_step": round(r[2], 3),
-                      "post_ms_per_step": round(r[3], 3)} for r in per_rank],
+                      "post_ms_per_step": round(r[3], 3) if args.full else None,
+                      "post_overlapped_ms_per_step": round(r[4], 3)} for r in per_rank],
         "roofline": {
             "bound": "mfma",
             "kernel": "BODY_25 CNN forward (113 halo implicit-GEMM conv launches + fused first "
@@ -822,14 +875,16 @@ def rank_main(args, rank, world, local):
             "algorithmic_gflop_per_launch": round(flops_frame * B / 1e9, 2),
             "avg_launch_ms": round(net_ms, 3),
             "measured_ceilings": peaks,
-            "frac_of_measured_random_operand_mfma": round(achieved / peaks["mfma_fp16_random_tflops"], 4),
+            "frac_of_measured_random_operand_mfma": (round(achieved / peaks["mfma_fp16_random_tflops"], 4)
+                                                     if peaks else None),
         },
         "post_roofline": (dict(post_roofline(B, post_ms), overlapped_event_span_ms=round(post_overlap_ms, 3))
-                          if nscales == 1 else None),
+                          if nscales == 1 and args.full else None),
         "host_ms": host_ms,
         "per_rank_host": rank_hosts,
     }
-    if rank == 0 and world == 1 and nscales == 1 and not args.no_cpu_baseline and args.precision == "fp16":
+    if (rank == 0 and world == 1 and nscales == 1 and args.full and not args.no_cpu_baseline
+            and args.precision == "fp16"):
         frames_np = frames[first_content][:2].cpu().numpy()   # uint8 [2][720][1280][3]
         result["cpu_baseline"] = cpu_baseline(args, params, frames_np, ov_np[first_content][:2])
         # keypoint parity at full strength on the same frames, fp16 and split precision, and the
@@ -843,8 +898,8 @@ def rank_main(args, rank, world, local):
         p16["precision"] = "fp16 (the measured product path)"
         psp["precision"] = "split (opk_net_set_precision OPK_PRECISION_SPLIT)"
         result["parity"] = dict(p16, split_precision=psp)
-    if (rank == 0 and world == 1 and nscales == 1 and args.precision == "fp16" and not args.no_extra_configs
-            and not args.dump_records and not args.collective_gather):
+    if (rank == 0 and world == 1 and nscales == 1 and args.precision == "fp16" and args.full
+            and not args.no_extra_configs and not args.dump_records and not args.collective_gather):
         result["configs"] = extra_legs(args)
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -935,6 +990,8 @@ def rank_main_body135(args, rank, world, local):
     npost, post_ms = pose.read_timing()
     pose.set_timing(False)
     post_ms /= max(npost, 1)
+    if rank == 0 and args.dump_outputs:   # the last timed step's batch is the last one collected
+        dump_outputs(args.dump_outputs, pose, B, 4 * people + 8)
     if dist is not None:
         tt = torch.tensor([elapsed, post_ms], device=comm_dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -979,7 +1036,7 @@ def rank_main_body135(args, rank, world, local):
         "host_ms": host_ms,
         "per_rank_host": rank_hosts,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         import oracle   # the CPU baseline leg only
         t_orc = oracle.pose_tables()[BODY_135]
         t1 = time.perf_counter()

@@ -300,6 +300,48 @@ def test_bench_content_depends_on_global_batch_only():
             assert have == {(s * world + rank) % bench.CONTENTS for s in range(12)}
 
 
+def test_bench_dump_outputs_layout(tmp_path):
+    """bench.py --dump-outputs: fixed-shape float32 arrays of the last batch (rows past a frame's
+    people stay 0) and an evenly spaced, fixed sample of the net output's frames."""
+    import bench
+    rng = np.random.default_rng(3)
+    per_frame = [(rng.random((n, 25, 3), np.float32), rng.random(n, np.float32))
+                 for n in (2, 0, 5) + (1,) * 37]
+    net_out = rng.random((40, 4, 3, 5), np.float32)
+
+    class Pose:
+        parts = 25
+
+        def keypoints(self, f):
+            return per_frame[f]
+
+    class Net:
+        def output_numpy(self):
+            return net_out
+
+    d = str(tmp_path / "out")
+    bench.dump_outputs(d, Pose(), 40, 6, Net())
+    got = {n[:-4]: np.load(os.path.join(d, n)) for n in sorted(os.listdir(d))}
+    assert sorted(got) == ["keypoints", "net_output", "net_output_frames", "people", "scores"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["keypoints"].shape == (40, 6, 25, 3) and got["scores"].shape == (40, 6)
+    np.testing.assert_array_equal(got["people"], [len(k) for k, _ in per_frame])
+    for f, (k, s) in enumerate(per_frame):
+        np.testing.assert_array_equal(got["keypoints"][f, :len(k)], k)
+        np.testing.assert_array_equal(got["scores"][f, :len(s)], s)
+        assert not got["keypoints"][f, len(k):].any() and not got["scores"][f, len(s):].any()
+    pick = got["net_output_frames"].astype(int)
+    assert len(pick) == bench.DUMP_NET_FRAMES and pick[0] == 0 and pick[-1] == 39
+    assert np.all(np.diff(pick) > 0)
+    np.testing.assert_array_equal(got["net_output"], net_out[pick])
+    # without a net (config 5: the net output is the caller's input) only the people are written
+    d2 = str(tmp_path / "out2")
+    bench.dump_outputs(d2, Pose(), 3, 6)
+    assert sorted(os.listdir(d2)) == ["keypoints.npy", "people.npy", "scores.npy"]
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(d2, Pose(), 3, 4)   # frame 2 holds 5 people
+
+
 def test_rank_cpus_disjoint_gpu_local_shares(monkeypatch):
     """every rank's people-assembly threads get a disjoint share of its GPU's
     NUMA-local CPUs (parallel.rank_cpus, applied by bench.py before any GPU call); the assembly

@@ -80,6 +80,44 @@ def test_alternating_net_outputs_same_records(tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and reports nothing that needs a run of
+    its own; --dump-outputs holds what the last timed step returned: the people of the gathered
+    records' last batch, bit for bit, and that batch's net output."""
+    batch, steps = 8, 3
+    rec, out = str(tmp_path / "rec.npz"), str(tmp_path / "out")
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "OPK_BENCH_REHEARSE"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                        "--batch", str(batch), "--dump-records", rec, "--dump-outputs", out],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == steps and line["config"]["frames_gathered_in_order"] == batch * steps
+    assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "fp16"
+    assert line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 / batch - 1) < 1e-3   # value = frames / s
+    for k in ("cpu_baseline", "parity", "configs"):
+        assert k not in line
+    assert line["post_roofline"] is None and line["roofline"]["measured_ceilings"] is None
+    assert line["roofline"]["achieved"] > 0   # (HIP events of the timed steps: no run of its own)
+    a = np.load(rec)
+    counts = a["counts"][-batch:]
+    first = int(a["counts"][:-batch].sum())
+    got = {n: np.load(os.path.join(out, n + ".npy")) for n in ("people", "keypoints", "scores", "net_output")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    np.testing.assert_array_equal(got["people"], counts)
+    assert counts.sum() >= batch   # people were found
+    kp = np.concatenate([got["keypoints"][f, :counts[f]] for f in range(batch)])
+    ks = np.concatenate([got["scores"][f, :counts[f]] for f in range(batch)])
+    np.testing.assert_array_equal(kp.reshape(-1), a["keypoints"][first * 75:])
+    np.testing.assert_array_equal(ks, a["scores"][first:])
+    assert got["net_output"].shape == (batch, 78, 46, 82) and np.isfinite(got["net_output"]).all()
+    assert got["net_output"].std() > 0
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("config", ["body25", "body135"])
 def test_rccl_gather_one_rank(config, tmp_path):
     """The RCCL transport of an N-GPU run, executed on the 1-GPU box: bench.py
