@@ -92,7 +92,8 @@ struct Conv3Shape {
     bool persist;                 // 16-wave tiles: persistent kernel (conv3p) when the launch allows
 };
 // w8: the conv may run on conv3w8 (conv3_w8_eligible): 64-output 3x3 layers of >= 768 tiles then
-// take the persistent 512-position geometry of the 8-wave kernel
+// take the persistent 512-position geometry of the 8-wave kernel -- unless its strip would be 16
+// virtual columns or narrower (conv3w8_supported needs more): those keep the 8-wave tiles
 Conv3Shape conv3_shape(int frames, int H, int W, int cout, int ks, int border = 1, bool w8 = false);
 // a 64-output 3x3 conv that conv3w8's BN = 64 instantiation can run (one aligned destination, no
 // fp32 output, a persistent sink): the planner and the launchers decide the same way from it

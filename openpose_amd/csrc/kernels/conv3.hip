@@ -777,6 +777,15 @@ Conv3Shape conv3_shape(int frames, int H, int W, int cout, int ks, int border, b
         // CU)
         const long tiles = ((long)frames * (H + 2 * border) * (W + 2 * border) / 256) *
                            ((cout + s.bn - 1) / s.bn);
+        // conv3w8 needs strips of more than 16 virtual columns (conv3w8_supported): a narrower
+        // 64-output layer is not taken there and keeps conv3_kernel's 8-wave geometry.  Decided
+        // here, from the strip the persistent halo would give, so that the planner, the frame
+        // runs and launch_conv3 (all callers of this function) agree
+        if (w8 && s.bn == 64) {
+            const int pstrip = (kP_HR - kP_BM - (ks - 1)) / (ks - 1) - 2 * border;
+            const int pn = pstrip > 0 ? (W + pstrip - 1) / pstrip : 1;
+            if ((W + pn - 1) / pn + 2 * border <= 16) w8 = false;
+        }
         // (measured, round 1: 4-wave 256x128 two-per-CU tiles and 8-wave 512x128 tiles of 128x64
         // wave tiles were both slower than these on every BODY_25 layer)
         if ((s.bn != 64 || w8) && big16 && tiles >= 3 * 256) {   // 512 x {128,96} tiles, 16 waves

@@ -21,29 +21,12 @@ import pytest
 import torch
 
 from oracle import body25
-from oracle import fp16 as emu
-from openpose_amd import synth
 from openpose_amd.api import Net, dev_switches
+from tests.launch_check import check_launches, random_params
 
 pytestmark = pytest.mark.gpu
 
-C_ACC = 2.0 ** -16          # one conv per kernel
-C_ACC_CHAINED = 2.0 ** -14  # conv1_1 -> conv1_2 and Mconv6 -> Mconv7 inside one kernel
-NET_H, NET_W = 368, 656
-
-
-def random_params(graph, seed):
-    """He weights + non-zero biases + PReLU slopes in (0.05, 0.5) (all in [0, 1]: the max
-    epilogue the bench runs)."""
-    params = synth.he_weights(graph, seed=seed)
-    rng = np.random.default_rng(seed + 1)
-    out = {}
-    for name, (w, b, s) in params.items():
-        b = rng.normal(0.0, 0.05, b.shape).astype(np.float32)
-        if s is not None:
-            s = rng.uniform(0.05, 0.5, s.shape).astype(np.float32)
-        out[name] = (w, b, s)
-    return out
+NET_H, NET_W = 368, 656   # (C_ACC, C_ACC_CHAINED, C_SPLIT: tests/launch_check.py)
 
 
 @pytest.fixture(scope="module")
@@ -86,73 +69,26 @@ def test_launch_log_covers_the_bench_kernels(bench_net):
     print("%d launches, %d instantiations: %s" % (len(log), len(inst), sorted(inst)))
 
 
-def _check_unit(bench_net, layer, kernel):
-    net, graph, params = bench_net["net"], bench_net["graph"], bench_net["params"]
-    u = emu.unit_from_launch(graph, layer)
-    chained = len(u["convs"]) > 1
-    worst = (0.0, 0.0, 0.0)
-    for f in bench_net["frames"]:
-        if u["input"] == "image":
-            x = bench_net["x"][f:f + 1]
-        else:
-            x = net.blob(u["input"], (f, 1))
-        got = net.blob(u["output"], (f, 1))
-        ref, tol = emu.unit(u, x, params, C_ACC_CHAINED if chained else C_ACC)
-        assert got.shape == ref.shape, (layer, got.shape, ref.shape)
-        d = np.abs(got - ref)
-        bad = d > tol
-        if bad.any():
-            i = np.unravel_index(np.argmax(d - tol), d.shape)
-            raise AssertionError("%s (%s) frame %d: %d of %d elements beyond the bound; worst at %s: "
-                                 "gpu %r ref %r tol %r" % (layer, kernel, f, int(bad.sum()), d.size,
-                                                           i, float(got[i]), float(ref[i]),
-                                                           float(tol[i])))
-        # in ulp16 where the output rounding dominates the bound (no cancellation)
-        ulp = emu.ulp16(ref)
-        dom = tol <= 3 * ulp
-        ulps = float((d[dom] / ulp[dom]).max()) if dom.any() else 0.0
-        worst = tuple(max(a, b) for a, b in zip(worst, (ulps, float((d / tol).max()),
-                                                        float(np.abs(ref).max()))))
-    return worst
-
-
 def test_every_launch_within_fp16_bound(bench_net, record_property):
     """Each launch of the bench forward against the fp16-storage emulation of its layers, fed with
     the GPU's own input blob (frames 0, middle, last).  Also the fp32 net_output slices of the two
-    final heads."""
-    rows = []
-    for layer, kernel in bench_net["log"]:
-        w = _check_unit(bench_net, layer, kernel)
-        rows.append((layer, kernel) + w)
-    for layer, kernel, ulps, frac, amax in rows:
+    final heads (tests/launch_check.py)."""
+    b = bench_net
+    rows = check_launches(b["net"], b["graph"], b["params"], b["x"], b["frames"], log=b["log"])
+    assert [r.layer for r in rows] == [layer for layer, _ in b["log"]]   # no stand-alone pool here
+    for r in rows:
         print("%-40s %-30s %.2f ulp16 (rounding-dominated elements)  %.3f of bound  |ref| <= %.3g"
-              % (layer, kernel, ulps, frac, amax))
-    record_property("max_ulp16", max(r[2] for r in rows))
-    record_property("max_frac_of_bound", max(r[3] for r in rows))
-    # net_output (fp32): the last heads' slices against the emulation from their own inputs
-    net, graph, params = bench_net["net"], bench_net["graph"], bench_net["params"]
-    off = 0
-    for b in [l for l in graph if l["top"][0] == "net_output"][0]["bottom"]:
-        head = [lay for lay, _ in bench_net["log"] if lay.endswith("+" + b)]
-        assert len(head) == 1, b
-        u = emu.unit_from_launch(graph, head[0])
-        u = dict(u, fp32_output=True)
-        for f in bench_net["frames"]:
-            ref, tol = emu.unit(u, net.blob(u["input"], (f, 1)), params, C_ACC_CHAINED)
-            got = net.blob("net_output", (f, 1))[:, off:off + ref.shape[1]]
-            assert (np.abs(got - ref) <= tol).all(), (b, f)
-        off += ref.shape[1]
-    assert off == 78
+              % (r.layer, r.kernel, r.ulp16, r.frac, r.amax))
+    record_property("max_ulp16", max(r.ulp16 for r in rows))
+    record_property("max_frac_of_bound", max(r.frac for r in rows))
+    assert b["net"].blob("net_output", (0, 1)).shape[1] == 78
 
 
 # ---- split precision (opk_net_set_precision OPK_PRECISION_SPLIT) --------------------------------
 # The same bench geometry in split precision: every conv launch -- conv_image<split>, the 8-wave
 # conv3w8 split instantiations (96 / 128 channels, 2 and 4 n-blocks), conv3_kernel split for the
 # rest -- against the exact (float64) conv of the GPU's own hi + lo input blob (oracle/split.py).
-# fp32 accumulation + dropped lo*lo + weight residue (oracle/split.py); the worst launch measured
-# 0.041 of 2^-16 (round 6, r6b), so 2^-19 keeps ~3x headroom -- a missing or misplaced pass
-# (~2^-11 S) is 250x beyond it
-C_SPLIT = 2.0 ** -19
+# C_SPLIT = 2^-19 (tests/launch_check.py)
 
 
 @pytest.fixture(scope="module")
@@ -205,34 +141,14 @@ def test_split_launch_log_uses_fused_kernels(split_net):
 
 def test_split_every_launch_within_bound(split_net, record_property):
     """Each conv launch of the split-precision bench forward against the float64 conv of the GPU's
-    own hi + lo input blob (frames 0 and last): |gpu - ref| <= 2^-19 S + 2^-21 |ref| + 2^-24."""
-    from oracle import split as sp
-    net, graph, params = split_net["net"], split_net["graph"], split_net["params"]
-    worst = 0.0
-    rows = []
-    for layer, kernel in split_net["log"]:
-        if layer == "pool":
-            continue
-        u = emu.unit_from_launch(graph, layer)
-        frac = 0.0
-        for f in split_net["frames"]:
-            x = split_net["x"][f:f + 1] if u["input"] == "image" else net.blob(u["input"], (f, 1))
-            ref, tol = sp.unit(u, x, params, C_SPLIT)
-            got = net.blob(u["output"], (f, 1))   # (hi + lo; net_output heads: fp32)
-            assert got.shape == ref.shape, (layer, got.shape, ref.shape)
-            d = np.abs(got.astype(np.float64) - ref)
-            bad = d > tol
-            if bad.any():
-                i = np.unravel_index(np.argmax(d - tol), d.shape)
-                raise AssertionError("%s (%s) frame %d: %d of %d elements beyond the split bound; "
-                                     "worst at %s: gpu %r ref %r tol %r"
-                                     % (layer, kernel, f, int(bad.sum()), d.size, i, float(got[i]),
-                                        float(ref[i]), float(tol[i])))
-            frac = max(frac, float((d / tol).max()))
-        rows.append((layer, kernel, frac))
-        worst = max(worst, frac)
-    for layer, kernel, frac in rows:
-        print("%-40s %-40s %.3f of bound" % (layer, kernel, frac))
-    record_property("report_max_frac_of_split_bound", round(worst, 4))
-    record_property("report_split_worst_launch", max(rows, key=lambda r: r[2])[:2])
-
+    own hi + lo input blob (frames 0 and last): |gpu - ref| <= 2^-19 S + 2^-21 |ref| + 2^-24; the
+    stand-alone pools exactly (tests/launch_check.py)."""
+    b = split_net
+    rows = check_launches(b["net"], b["graph"], b["params"], b["x"], b["frames"], split=True,
+                          log=b["log"])
+    assert {r.layer for r in rows} >= {layer for layer, _ in b["log"] if layer != "pool"}
+    for r in rows:
+        print("%-40s %-40s %.3f of bound" % (r.layer, r.kernel, r.frac))
+    worst = max(rows, key=lambda r: r.frac)
+    record_property("report_max_frac_of_split_bound", round(worst.frac, 4))
+    record_property("report_split_worst_launch", (worst.layer, worst.kernel))
