@@ -240,8 +240,8 @@ int opk_cvmat_to_input(opk_ctx* ctx, float* input_dev, const uint8_t* frames_dev
 
 /* Kernel-variant switches (no reference counterpart; A/B tests and tuning only): key = one of
  * "CONV3_SMALL", "CONV3_W16", "CONV3_PERSIST", "CONV3_WIDE", "CONV3P_ASMR", "CONV3P_WIDE",
- * "CONV3P_PRIO", "CONV3W", "CONV1_TILE", "CONV1_N64W16", "CONV1_FUSED" (read when a launch is
- * planned);
+ * "CONV3P_PRIO", "CONV3W", "CONV1_TILE", "CONV1_N64W16", "CONV1_FUSED", "CONV3S_MAX" (read when a
+ * launch is planned);
  * reset != 0 removes the key (back to the product default).  Process-wide; the environment is
  * never consulted. */
 int opk_dev_set(const char* key, int value, int reset);
@@ -290,6 +290,20 @@ int opk_net_flops_per_frame(opk_net* net, int h, int w, double* flops);
 #define OPK_PRECISION_FP16 0
 #define OPK_PRECISION_SPLIT 1
 int opk_net_set_precision(opk_net* net, int precision);
+/* Small-batch mode (no reference counterpart).  The default planning tiles every 3x3 conv for the
+ * large batches of opk_pose_submit (256 or 512 positions x 64..128 outputs): a forward of one
+ * frame, as op::PoseExtractorCaffe::forwardPass runs it, leaves most compute units idle.
+ * 0 (default): today's planning.  1: 3x3 layers that would not fill the chip run on conv3s tiles;
+ * results are bit-identical either way.  Re-plans the net's shapes. */
+int opk_net_set_small_batch(opk_net* net, int enable);   /* other values: OPK_ERR_ARG */
+int opk_net_small_batch(opk_net* net);                    /* 0 / 1, -1 for NULL */
+/* Host-only (works on a device -1 context): the conv geometry the planner picks for conv `index`
+ * (opk_net_conv_info order) of an n x h x w forward on a chip of `cus` compute units: the GEMM
+ * tile bm positions x bn outputs and `workgroups`, the tiles of the frames' h x (w + 2) positions
+ * times the n-blocks (the launched grid also covers border rows; persistent kernels launch at
+ * most `cus`).  The image conv has no GEMM tile and reports zeros.  Any output may be NULL. */
+int opk_net_conv_plan(opk_net* net, int index, int n, int h, int w, int cus,
+                      int* bm, int* bn, int* workgroups, int* small /* 1: conv3s */);
 /* Forward timing (measurement hook, no reference counterpart): while enabled every forward is
  * bracketed by HIP events on the context stream; read waits for them and returns the number of
  * forwards since the last read and their summed device time in milliseconds. */

@@ -122,6 +122,23 @@ namespace op
                 opk_net_destroy(net);   // not leaked on the error path
                 error(std::string{"libopk_hip: "} + msg, __LINE__, __FUNCTION__, __FILE__);
             }
+            // OPENPOSE_HIP_SMALL_BATCH=1: every net of the process (pose, face, hand) in small-batch
+            // mode (opk_net_set_small_batch: forwardPass runs one frame at a time); unset or "0"
+            // keeps the default, any other value is an error
+            const char* sbEnv = std::getenv("OPENPOSE_HIP_SMALL_BATCH");
+            const std::string smallBatch = sbEnv ? sbEnv : "0";
+            if (smallBatch != "0" && smallBatch != "1")
+            {
+                opk_net_destroy(net);
+                error("OPENPOSE_HIP_SMALL_BATCH must be 0 or 1, not '" + smallBatch + "'.", __LINE__,
+                      __FUNCTION__, __FILE__);
+            }
+            if (smallBatch == "1" && opk_net_set_small_batch(net, 1) != OPK_OK)
+            {
+                const std::string msg = opk_last_error();
+                opk_net_destroy(net);
+                error(std::string{"libopk_hip: "} + msg, __LINE__, __FUNCTION__, __FILE__);
+            }
             return net;
         }
 

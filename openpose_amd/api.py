@@ -449,6 +449,22 @@ class Net:
         the MFMA work; opk_net_set_precision)."""
         check(self.L.opk_net_set_precision(self.h, int(precision)))
 
+    def set_small_batch(self, on=True):
+        """Small-batch mode (opk_net_set_small_batch): 3x3 layers that would not fill the chip run
+        on conv3s tiles; the results are bit-identical."""
+        check(self.L.opk_net_set_small_batch(self.h, int(bool(on))))
+
+    @property
+    def small_batch(self):
+        return self.L.opk_net_small_batch(self.h) == 1
+
+    def conv_plan(self, index, n, h, w, cus):
+        """{bm, bn, workgroups, small} the planner picks for conv `index` (convs() order) of an
+        n x h x w forward on a chip of `cus` compute units (opk_net_conv_plan; host-only)."""
+        v = [ctypes.c_int() for _ in range(4)]
+        check(self.L.opk_net_conv_plan(self.h, index, n, h, w, cus, *[ctypes.byref(x) for x in v]))
+        return dict(bm=v[0].value, bn=v[1].value, workgroups=v[2].value, small=v[3].value)
+
     def set_timing(self, on=True):
         check(self.L.opk_net_set_timing(self.h, int(on)))
 

@@ -405,6 +405,30 @@ int opk_net_set_precision(opk_net* net, int precision)
     });
 }
 
+int opk_net_set_small_batch(opk_net* net, int enable)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(net, "NULL net");
+        OPK_CHECK_ARG(enable == 0 || enable == 1, "small batch: 0 or 1");
+        net->net->set_small_batch(enable == 1);
+    });
+}
+
+int opk_net_small_batch(opk_net* net)
+{
+    if (!net) return -1;
+    return net->net->small_batch() ? 1 : 0;
+}
+
+int opk_net_conv_plan(opk_net* net, int index, int n, int h, int w, int cus, int* bm, int* bn,
+                      int* workgroups, int* small)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(net, "NULL net");
+        net->net->conv_plan(index, n, h, w, cus, bm, bn, workgroups, small);
+    });
+}
+
 int opk_net_set_timing(opk_net* net, int enable)
 {
     return guarded_net([&] {

@@ -316,6 +316,76 @@ void NetHip::set_precision(int precision)
     cur_ = nullptr;
 }
 
+void NetHip::set_small_batch(bool on)
+{
+    if (on == small_batch_) return;
+    small_batch_ = on;
+    shapes_.clear();   // re-plan the shapes, as set_precision does
+    cur_ = nullptr;
+}
+
+bool NetHip::fused1_at(int h, int w) const
+{
+    // CONV1_FUSED=0 (opk_dev_set, A/B tests): the three separate kernels instead of the fusion
+    // (split precision: no conv1 fusion)
+    return precision_ != kPrecisionSplit && fuse1_.a >= 0 && dev_switch("CONV1_FUSED", 1) != 0 &&
+           border_ == 1 && conv1_fused_supported(h, w, 64, 64);
+}
+
+bool NetHip::w8_eligible(const ConvPlan& c) const
+{
+    std::vector<int> dcs, dco;
+    for (const auto& o : c.outs) {
+        dcs.push_back(bufs_[o.buf].cs);
+        dco.push_back(o.coff);
+    }
+    return !dcs.empty() && conv3_w8_eligible(c.info.cout, c.ntaps, (int)c.outs.size(), dcs.data(),
+                                             dco.data(), c.out32_coff >= 0);
+}
+
+Conv3sShape NetHip::small_pick(int ci, int n, int H, int W, int cus, bool fused1) const
+{
+    const ConvPlan& c = convs_[ci];
+    Conv3sShape none{};
+    // 3x3 convs that run as launches of their own (the fused units are planned as without the mode)
+    if (!small_batch_ || c.from_image || c.ntaps != 9 || c.cin_pad % 32 != 0) return none;
+    if (fused1 && (ci == fuse1_.a || ci == fuse1_.b)) return none;
+    return conv3s_pick(n, H, W, c.info.cout, border_, cus, w8_eligible(c));
+}
+
+void NetHip::conv_plan(int index, int n, int h, int w, int cus, int* bm, int* bn, int* workgroups,
+                       int* small) const
+{
+    OPK_CHECK_ARG(index >= 0 && index < (int)convs_.size(), "bad index");
+    OPK_CHECK_ARG(n > 0 && h > 0 && w > 0 && cus > 0, "bad shape");
+    const ConvPlan& c = convs_[index];
+    int H = h, W = w;
+    for (int l = 0; l < c.level; ++l) {   // Caffe ceil sizing for 2x2/2 pooling
+        H = (H - 2 + 1) / 2 + 1;
+        W = (W - 2 + 1) / 2 + 1;
+    }
+    int pbm = 0, pbn = 0, psmall = 0;
+    long wg = 0;
+    if (!c.from_image) {   // (the image conv has no GEMM tile: zeros)
+        const Conv3sShape ss = small_pick(index, n, H, W, cus, fused1_at(h, w));
+        if (ss.ok) {
+            pbm = ss.bm;
+            pbn = ss.bn;
+            wg = ss.workgroups;
+            psmall = 1;
+        } else {
+            const Conv3Shape s3 = conv3_shape(n, H, W, c.info.cout, c.info.k, border_, w8_eligible(c));
+            pbm = s3.bm;
+            pbn = s3.bn;
+            wg = conv3_fill(s3, n, H, W, c.info.cout);
+        }
+    }
+    if (bm) *bm = pbm;
+    if (bn) *bn = pbn;
+    if (workgroups) *workgroups = (int)std::min<long>(wg, 0x7fffffff);
+    if (small) *small = psmall;
+}
+
 void NetHip::pack(ConvPlan& c)
 {
     const std::string& name = c.info.name;
@@ -497,10 +567,8 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
     }
     std::vector<uint16_t*>& ptr = S.base;
     ptr.assign(bufs_.size(), nullptr);
-    // CONV1_FUSED=0 (opk_dev_set, A/B tests): the three separate kernels instead of the fusion
-    S.split = precision_ == kPrecisionSplit;   // (split precision: no conv1 fusion)
-    S.fused1 = !S.split && fuse1_.a >= 0 && dev_switch("CONV1_FUSED", 1) != 0 && border_ == 1 &&
-               conv1_fused_supported(h, w, 64, 64);
+    S.split = precision_ == kPrecisionSplit;
+    S.fused1 = fused1_at(h, w);
     // HEAD_FUSE=0 (opk_dev_set, A/B tests): Mconv6 and Mconv7 as two conv3 launches
     // Positions are decoded by float-reciprocal division in conv_head_kernel, exact below 2^24:
     // larger batches run the pairs unfused.
@@ -590,13 +658,7 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
         OPK_CHECK_ARG(use3 || c.w.ptr != nullptr, c.info.name + ": weights not set");
         if (use3) {
             // (conv3w8's 64-output tile: decided from the destinations as launch_conv3 decides)
-            std::vector<int> dcs, dco;
-            for (const auto& o : c.outs) {
-                dcs.push_back(bufs_[o.buf].cs);
-                dco.push_back(o.coff);
-            }
-            const bool w8 = !dcs.empty() && conv3_w8_eligible(c.info.cout, a.ntaps, (int)c.outs.size(),
-                                                              dcs.data(), dco.data(), c.out32_coff >= 0);
+            const bool w8 = w8_eligible(c);
             const Conv3Shape s3 = conv3_shape(n, H, W, c.info.cout, c.info.k, border_, w8);
             a.sw = s3.sw;
             a.nstrips = s3.nstrips;
@@ -639,6 +701,17 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
             a.out32 = S.out32;
             a.out32_c = out_c_;
             a.out32_coff = c.out32_coff;
+        }
+        // small-batch mode: conv3s tiles where conv3_shape's leave most of the chip idle
+        if (use3 && !a.pool) {
+            const Conv3sShape ss = small_pick((int)ci, n, H, W, a.cus, S.fused1);
+            if (ss.ok) {
+                ConvArgs t = a;
+                t.small = 1;
+                t.sw = ss.sw;
+                t.nstrips = ss.nstrips;
+                if (conv3s_supported(t)) a = t;
+            }
         }
     }
     return &S;
@@ -785,6 +858,10 @@ static void launch_conv3_frames(const ConvArgs& a, hipStream_t st)
 {
     const int B = a.border > 0 ? a.border : 1;
     const int ks = a.ntaps == 49 ? 7 : (a.ntaps == 9 ? 3 : 1);
+    if (a.small) {   // planned on conv3s tiles (whole batch: conv3s_supported checked its range)
+        launch_conv3s(a, st);
+        return;
+    }
     if (conv3_run_fits(a, a.frames, ks, B)) {
         launch_conv3(a, st);
         return;

@@ -30,6 +30,16 @@ public:
     static constexpr int kPrecisionFp16 = 0, kPrecisionSplit = 1;
     void set_precision(int precision);
     int precision() const { return precision_; }
+    // Small-batch mode (off by default): 3x3 convs whose conv3_shape geometry gives fewer
+    // workgroups than the chip has CUs run on conv3s tiles (conv3s_pick, conv.h) -- the same
+    // bits, more of the chip busy when a forward is a frame or a few.  Re-plans the shapes.
+    void set_small_batch(bool on);
+    bool small_batch() const { return small_batch_; }
+    // host-only: the GEMM tile, fill measure (conv3_fill) and kernel family (small: conv3s) the
+    // planner picks for conv `index` of an n x h x w forward on a chip of cus compute units
+    // (the image conv: zeros)
+    void conv_plan(int index, int n, int h, int w, int cus, int* bm, int* bn, int* workgroups,
+                   int* small) const;
     bool ready() const;
     // caffe::Net::CopyTrainedLayersFrom (netCaffe.cpp:165,185): weights, bias and PReLU slopes of
     // every conv named in the file (shapes checked as Caffe does); layers the net does not have
@@ -108,6 +118,10 @@ private:
         float wscale = 1.f;   // split precision: 2^-e of the packed weights' scaling (ConvArgs::wscale)
         std::vector<float> hw, hb, hs;   // host copies of the weights (re-packed per precision)
     };
+    bool fused1_at(int h, int w) const;            // conv1_fused_kernel runs at this input size
+    bool w8_eligible(const ConvPlan& c) const;     // conv3_w8_eligible of the conv's destinations
+    // the conv3s geometry of conv ci at n x H x W (its level's size), ok == false: conv3_shape's
+    Conv3sShape small_pick(int ci, int n, int H, int W, int cus, bool fused1) const;
     void pack(ConvPlan& c);   // device layouts of one conv's weights for the current precision
     struct PoolPlan { int in_buf, out_buf, level_in, channels; };
     struct Step { bool conv; int idx; };
@@ -159,6 +173,7 @@ private:
     std::vector<int> pool_conv_;
     int cus_ = 256;               // compute units (persistent-kernel grid)
     int precision_ = kPrecisionFp16;
+    bool small_batch_ = false;    // set_small_batch
     int border_ = 1;              // zero border of every padded image (widest conv pad, >= 1)
 
     struct BlobLoc { int buf = -1, coff = 0, ch = 0, level = 0; bool out32 = false; };

@@ -68,6 +68,8 @@ struct ConvArgs {
     const uint16_t* in_lo;
     uint16_t* dst_lo[kConvMaxDst];
     float wscale;
+    int small;            // planned on conv3s tiles (NetHip small-batch mode): sw / nstrips are conv3s_shape's
+    int pbn;              // conv3s only, set by launch_conv3s: the n-block of the weight packing
 };
 // the product of a split virtual chunk (3c + k) that reads w_lo: k = 0 (the order above; dev A/B
 // builds: OPK_SPLIT_WLO_K=1, the round-6 order x_hi w_hi, x_hi w_lo, x_lo w_hi, every product
@@ -111,6 +113,28 @@ void launch_conv3w(const ConvArgs& a, hipStream_t stream);
 bool conv3w8_supported(const ConvArgs& a);
 bool conv3w8_pool_supported(const ConvArgs& a);
 void launch_conv3w8(const ConvArgs& a, hipStream_t stream);
+// conv3s.hip: 3x3 / border 1 convs on small tiles (64 x 32 or 128 x 64, 4 waves), bit-identical to
+// the kernels above, for forwards too small to fill the chip with conv3_shape's tiles.
+// conv3_fill / Conv3sShape::workgroups: the planner's measure of how far a geometry fills the chip,
+// tiles of the GEMM's M = frames * H * (W + 2) positions times n-blocks (the launched grid also
+// covers the border rows and the strips' shared columns: a few per cent more).
+struct Conv3sShape {
+    bool ok;                 // false: not supported (the conv keeps conv3_shape's geometry)
+    int bm, bn, hr, tapu;    // tile, halo rows, taps per K unit
+    int pbn;                 // n-block of the weight packing (conv3_shape's bn)
+    int sw, nstrips;
+    long workgroups, grid;   // fill measure; workgroups launched
+};
+long conv3_fill(const Conv3Shape& s, int frames, int H, int W, int cout);
+Conv3sShape conv3s_shape(int frames, int H, int W, int cout, int border, int cus);
+// the small-batch rule (planner, launcher and opk_net_conv_plan): ok when conv3_shape's geometry
+// (w8 as there) gives fewer than cus workgroups and conv3s supports the conv and gives more, but
+// no more than kConv3sMaxPerCu per CU (measured: the 64 x 32 tile is level with conv3_shape's at
+// 2.8 workgroups per CU and 1.8x slower at 5.7)
+constexpr int kConv3sMaxPerCu = 4;
+Conv3sShape conv3s_pick(int frames, int H, int W, int cout, int border, int cus, bool w8);
+bool conv3s_supported(const ConvArgs& a);
+void launch_conv3s(const ConvArgs& a, hipStream_t stream);
 
 // conv_head.hip: Mconv6 (1x1, n1 = 256 / 512 outputs, act6) -> Mconv7 (1x1, n2 <= 64 outputs) in
 // one kernel; the Mconv6 activations never leave the chip.  Input / outputs as ConvArgs (padded
