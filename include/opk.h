@@ -304,6 +304,17 @@ int opk_net_small_batch(opk_net* net);                    /* 0 / 1, -1 for NULL 
  * most `cus`).  The image conv has no GEMM tile and reports zeros.  Any output may be NULL. */
 int opk_net_conv_plan(opk_net* net, int index, int n, int h, int w, int cus,
                       int* bm, int* bn, int* workgroups, int* small /* 1: conv3s */);
+/* Host-only, the same shape arguments: which kernels such a forward launches for conv `index`, one
+ * "<kernel>\n" line per launch in launch order, with the buffer convention of opk_net_launch_log.
+ * A line is the launch log's kernel name up to the template arguments the planner fixes: the
+ * whole instantiation for conv3_kernel and conv3s_kernel, "conv3w8_kernel<BN,NB,POOL",
+ * "conv3w_kernel<BN" and "conv3p_kernel<BN" for the persistent kernels (the launch log's name
+ * starts with it).  A conv split into frame runs gives one line per run; a conv inside
+ * conv1_fused_kernel or conv_head_kernel gives that kernel's bare name on the unit's first conv
+ * and no line on the others; the image conv outside the fused unit gives conv_image_kernel.  The
+ * launchers take the kernel from the same plan, so the log of a real forward cannot differ. */
+int opk_net_conv_kernels(opk_net* net, int index, int n, int h, int w, int cus,
+                         char* buf, size_t size, size_t* needed);
 /* Forward timing (measurement hook, no reference counterpart): while enabled every forward is
  * bracketed by HIP events on the context stream; read waits for them and returns the number of
  * forwards since the last read and their summed device time in milliseconds. */

@@ -92,6 +92,7 @@ _SIGS = {
     "opk_net_set_small_batch": (_i, [_p, _i]),
     "opk_net_small_batch": (_i, [_p]),
     "opk_net_conv_plan": (_i, [_p, _i, _i, _i, _i, _i, _ip, _ip, _ip, _ip]),
+    "opk_net_conv_kernels": (_i, [_p, _i, _i, _i, _i, _i, _c.c_char_p, _c.c_size_t, _c.POINTER(_c.c_size_t)]),
     "opk_pose_records":(_i, [_p, _p, _c.c_size_t, _c.POINTER(_c.c_size_t)]),
     "opk_pose_heatmaps": (_i, [_p, _c.POINTER(_p), _ip]),
     "opk_pose_peaks": (_i, [_p, _c.POINTER(_p), _ip]),

@@ -465,6 +465,16 @@ class Net:
         check(self.L.opk_net_conv_plan(self.h, index, n, h, w, cus, *[ctypes.byref(x) for x in v]))
         return dict(bm=v[0].value, bn=v[1].value, workgroups=v[2].value, small=v[3].value)
 
+    def conv_kernels(self, index, n, h, w, cus):
+        """Launch-log name prefixes of the launches such a forward makes for conv `index`, in
+        launch order (opk_net_conv_kernels; host-only): one per frame run, none for a conv inside
+        another conv's fused kernel."""
+        need = ctypes.c_size_t()
+        check(self.L.opk_net_conv_kernels(self.h, index, n, h, w, cus, None, 0, ctypes.byref(need)))
+        buf = ctypes.create_string_buffer(need.value)
+        check(self.L.opk_net_conv_kernels(self.h, index, n, h, w, cus, buf, need.value, ctypes.byref(need)))
+        return buf.value.decode().splitlines()
+
     def set_timing(self, on=True):
         check(self.L.opk_net_set_timing(self.h, int(on)))
 

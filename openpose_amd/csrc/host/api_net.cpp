@@ -429,6 +429,18 @@ int opk_net_conv_plan(opk_net* net, int index, int n, int h, int w, int cus, int
     });
 }
 
+int opk_net_conv_kernels(opk_net* net, int index, int n, int h, int w, int cus, char* buf, size_t size,
+                         size_t* needed)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(net && needed, "NULL argument");
+        std::string text;
+        for (const auto& k : net->net->conv_kernels(index, n, h, w, cus)) text += k + "\n";
+        *needed = text.size() + 1;
+        if (buf && size >= *needed) std::memcpy(buf, text.c_str(), text.size() + 1);
+    });
+}
+
 int opk_net_set_timing(opk_net* net, int enable)
 {
     return guarded_net([&] {

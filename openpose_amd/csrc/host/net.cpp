@@ -332,25 +332,75 @@ bool NetHip::fused1_at(int h, int w) const
            border_ == 1 && conv1_fused_supported(h, w, 64, 64);
 }
 
-bool NetHip::w8_eligible(const ConvPlan& c) const
+NetHip::Dispatch NetHip::dispatch(int n, int h, int w, int cus) const
 {
-    std::vector<int> dcs, dco;
-    for (const auto& o : c.outs) {
-        dcs.push_back(bufs_[o.buf].cs);
-        dco.push_back(o.coff);
+    Dispatch D;
+    D.lh.assign(nlevels_, 0);
+    D.lw.assign(nlevels_, 0);
+    D.lh[0] = h;
+    D.lw[0] = w;
+    for (int l = 1; l < nlevels_; ++l) {   // Caffe ceil sizing for 2x2/2 pooling
+        D.lh[l] = (D.lh[l - 1] - 2 + 1) / 2 + 1;
+        D.lw[l] = (D.lw[l - 1] - 2 + 1) / 2 + 1;
     }
-    return !dcs.empty() && conv3_w8_eligible(c.info.cout, c.ntaps, (int)c.outs.size(), dcs.data(),
-                                             dco.data(), c.out32_coff >= 0);
-}
-
-Conv3sShape NetHip::small_pick(int ci, int n, int H, int W, int cus, bool fused1) const
-{
-    const ConvPlan& c = convs_[ci];
-    Conv3sShape none{};
-    // 3x3 convs that run as launches of their own (the fused units are planned as without the mode)
-    if (!small_batch_ || c.from_image || c.ntaps != 9 || c.cin_pad % 32 != 0) return none;
-    if (fused1 && (ci == fuse1_.a || ci == fuse1_.b)) return none;
-    return conv3s_pick(n, H, W, c.info.cout, border_, cus, w8_eligible(c));
+    D.split = precision_ == kPrecisionSplit;
+    D.fused1 = fused1_at(h, w);
+    // HEAD_FUSE=0 (opk_dev_set, A/B tests): Mconv6 and Mconv7 as two conv3 launches
+    // Positions are decoded by float-reciprocal division in conv_head_kernel: larger batches run
+    // the pairs unfused.
+    // (split precision: conv_head_kernel's split instantiations; HEAD_FUSE_SPLIT=0, dev A/B: the
+    // unfused split pair)
+    D.fusedh = (!D.split || dev_switch("HEAD_FUSE_SPLIT", 1) != 0) && !heads_.empty() &&
+               dev_switch("HEAD_FUSE", 1) != 0;
+    for (const auto& fh : heads_) {
+        const int L = convs_[fh.a].level;
+        D.fusedh = D.fusedh && conv_positions_fit((long)n * (D.lh[L] + 2) * (D.lw[L] + 2));
+    }
+    D.poolfused.assign(pools_.size(), 0);
+    D.query.assign(convs_.size(), Conv3Query{});
+    D.conv.assign(convs_.size(), Conv3Plan{});
+    for (size_t ci = 0; ci < convs_.size(); ++ci) {
+        const ConvPlan& c = convs_[ci];
+        if (c.from_image) continue;
+        Conv3Query& q = D.query[ci];
+        q.frames = n;
+        q.H = D.lh[c.level];
+        q.W = D.lw[c.level];
+        q.cout = c.info.cout;
+        q.cin_pad = c.cin_pad;
+        q.ntaps = c.ntaps;
+        q.border = border_;
+        q.ndst = (int)c.outs.size();
+        for (size_t d = 0; d < c.outs.size(); ++d) {
+            q.dst_cs[d] = bufs_[c.outs[d].buf].cs;
+            q.dst_coff[d] = c.outs[d].coff;
+        }
+        q.out32 = c.out32_coff >= 0;
+        q.split = D.split;
+        q.sink = true;
+        q.cus = cus;
+        // small-batch mode: 3x3 convs that run as launches of their own (the fused units are
+        // planned as without the mode)
+        q.small = small_batch_ && c.ntaps == 9 && c.cin_pad % 32 == 0 &&
+                  !(D.fused1 && ((int)ci == fuse1_.a || (int)ci == fuse1_.b));
+        // a pool fed by this conv alone runs in its epilogue where the plan, asked for it, has the
+        // pooled kernel (POOL_FUSE=0, opk_dev_set, A/B tests: the pools as their own kernels)
+        for (size_t p = 0; p < pools_.size(); ++p) {
+            if (pool_conv_[p] != (int)ci || dev_switch("POOL_FUSE", 1) == 0) continue;
+            if (D.fused1 && (int)p == fuse1_.p) continue;   // (pool1 inside conv1_fused_kernel)
+            Conv3Query qp = q;
+            qp.pool = true;   // the pooled image instead
+            qp.ndst = 1;
+            qp.dst_cs[0] = bufs_[pools_[p].out_buf].cs;
+            qp.dst_coff[0] = 0;
+            if (conv3_plan(qp).pool) {
+                q = qp;
+                D.poolfused[p] = 1;
+            }
+        }
+        D.conv[ci] = conv3_plan(q);
+    }
+    return D;
 }
 
 void NetHip::conv_plan(int index, int n, int h, int w, int cus, int* bm, int* bn, int* workgroups,
@@ -358,33 +408,35 @@ void NetHip::conv_plan(int index, int n, int h, int w, int cus, int* bm, int* bn
 {
     OPK_CHECK_ARG(index >= 0 && index < (int)convs_.size(), "bad index");
     OPK_CHECK_ARG(n > 0 && h > 0 && w > 0 && cus > 0, "bad shape");
-    const ConvPlan& c = convs_[index];
-    int H = h, W = w;
-    for (int l = 0; l < c.level; ++l) {   // Caffe ceil sizing for 2x2/2 pooling
-        H = (H - 2 + 1) / 2 + 1;
-        W = (W - 2 + 1) / 2 + 1;
-    }
-    int pbm = 0, pbn = 0, psmall = 0;
-    long wg = 0;
-    if (!c.from_image) {   // (the image conv has no GEMM tile: zeros)
-        const Conv3sShape ss = small_pick(index, n, H, W, cus, fused1_at(h, w));
-        if (ss.ok) {
-            pbm = ss.bm;
-            pbn = ss.bn;
-            wg = ss.workgroups;
-            psmall = 1;
-        } else {
-            const Conv3Shape s3 = conv3_shape(n, H, W, c.info.cout, c.info.k, border_, w8_eligible(c));
-            pbm = s3.bm;
-            pbn = s3.bn;
-            wg = conv3_fill(s3, n, H, W, c.info.cout);
-        }
-    }
-    if (bm) *bm = pbm;
-    if (bn) *bn = pbn;
-    if (workgroups) *workgroups = (int)std::min<long>(wg, 0x7fffffff);
-    if (small) *small = psmall;
+    Conv3Plan p{};   // (the image conv has no GEMM tile: zeros)
+    if (!convs_[index].from_image) p = dispatch(n, h, w, cus).conv[index];
+    if (bm) *bm = p.bm;
+    if (bn) *bn = p.bn;
+    if (workgroups) *workgroups = (int)std::min<long>(p.workgroups, 0x7fffffff);
+    if (small) *small = p.family == Conv3Family::conv3s;
 }
+
+std::vector<std::string> NetHip::conv_kernels(int index, int n, int h, int w, int cus) const
+{
+    OPK_CHECK_ARG(index >= 0 && index < (int)convs_.size(), "bad index");
+    OPK_CHECK_ARG(n > 0 && h > 0 && w > 0 && cus > 0, "bad shape");
+    const ConvPlan& c = convs_[index];
+    const Dispatch D = dispatch(n, h, w, cus);
+    if (D.fused1 && (index == fuse1_.a || index == fuse1_.b))
+        return index == fuse1_.a ? std::vector<std::string>{kConv1FusedKernel} : std::vector<std::string>{};
+    if (D.fusedh && c.head >= 0)
+        return index == heads_[c.head].a ? std::vector<std::string>{kConvHeadKernel} : std::vector<std::string>{};
+    if (c.from_image) return {kConvImageKernel};
+    std::vector<std::string> out;
+    Conv3Query q = D.query[index];
+    const int run = conv3_run_frames(q);
+    for (int f0 = 0; f0 < n; f0 += run) {   // as launch_conv3_frames
+        q.frames = std::min(run, n - f0);
+        out.push_back(conv3_plan(q).name);
+    }
+    return out;
+}
+
 
 void NetHip::pack(ConvPlan& c)
 {
@@ -438,7 +490,7 @@ void NetHip::pack(ConvPlan& c)
     // three products per chunk read w_hi, w_lo, w_hi (ConvArgs::split)
     std::vector<uint16_t> packed3;
     if (!c.from_image) {
-        const int BN = conv3_shape(1, 1, 1, c.info.cout, k, border_).bn;   // BN depends on cout only
+        const int BN = conv3_pack_bn(c.info.cout, k);
         const int nb = (c.info.cout + BN - 1) / BN, cpt = c.cin_pad / 32, kt = k * k;
         const int passes = split ? 2 : 1;
         packed3.assign((size_t)nb * passes * cpt * kt * BN * 32, 0);
@@ -552,55 +604,18 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
     }
     shapes_.push_back(std::make_unique<ShapePlan>());
     ShapePlan& S = *shapes_.back();
+    // what runs (host only), then the memory and the pointers
+    // GRID_CUS (opk_dev_set, dev): persistent grids of fewer CUs, e.g. two pipelines on
+    // concurrent streams sharing the chip
+    const int cus = std::min(cus_, std::max(1, dev_switch("GRID_CUS", cus_)));
+    static_cast<Dispatch&>(S) = dispatch(n, h, w, cus);
     S.n = n;
     S.h = h;
     S.w = w;
-    std::vector<int>& lh_ = S.lh;
-    std::vector<int>& lw_ = S.lw;
-    lh_.assign(nlevels_, 0);
-    lw_.assign(nlevels_, 0);
-    lh_[0] = h;
-    lw_[0] = w;
-    for (int l = 1; l < nlevels_; ++l) {   // Caffe ceil sizing for 2x2/2 pooling
-        lh_[l] = (lh_[l - 1] - 2 + 1) / 2 + 1;
-        lw_[l] = (lw_[l - 1] - 2 + 1) / 2 + 1;
-    }
+    const std::vector<int>& lh_ = S.lh;
+    const std::vector<int>& lw_ = S.lw;
     std::vector<uint16_t*>& ptr = S.base;
     ptr.assign(bufs_.size(), nullptr);
-    S.split = precision_ == kPrecisionSplit;
-    S.fused1 = fused1_at(h, w);
-    // HEAD_FUSE=0 (opk_dev_set, A/B tests): Mconv6 and Mconv7 as two conv3 launches
-    // Positions are decoded by float-reciprocal division in conv_head_kernel, exact below 2^24:
-    // larger batches run the pairs unfused.
-    // (split precision: conv_head_kernel's split instantiations; HEAD_FUSE_SPLIT=0, dev A/B: the
-    // unfused split pair)
-    S.fusedh = (!S.split || dev_switch("HEAD_FUSE_SPLIT", 1) != 0) && !heads_.empty() &&
-               dev_switch("HEAD_FUSE", 1) != 0;
-    for (const auto& fh : heads_) {
-        const int L = convs_[fh.a].level;
-        S.fusedh = S.fusedh && (long)n * (lh_[L] + 2) * (lw_[L] + 2) < (1L << 24);
-    }
-    // POOL_FUSE=0 (opk_dev_set, A/B tests): the pools as their own kernels
-    S.poolfused.assign(pools_.size(), 0);
-    for (size_t q = 0; q < pools_.size(); ++q) {
-        const int ci = pool_conv_[q];
-        if (ci < 0 || dev_switch("POOL_FUSE", 1) == 0) continue;
-        if (S.fused1 && (int)q == fuse1_.p) continue;   // (pool1 inside conv1_fused_kernel)
-        const ConvPlan& c = convs_[ci];
-        const int H = lh_[c.level], W = lw_[c.level];
-        // (64 outputs: conv3w8's BN = 64 tile, when the conv may take it -- conv3_w8_eligible)
-        std::vector<int> pcs, pco;
-        for (const auto& o : c.outs) {
-            pcs.push_back(bufs_[o.buf].cs);
-            pco.push_back(o.coff);
-        }
-        const bool w8 = !pcs.empty() && conv3_w8_eligible(c.info.cout, c.ntaps, (int)c.outs.size(),
-                                                          pcs.data(), pco.data(), c.out32_coff >= 0);
-        const Conv3Shape s3 = conv3_shape(n, H, W, c.info.cout, 3, border_, w8);
-        S.poolfused[q] = s3.persist && s3.nw == 16 && H % 2 == 0 && W % 2 == 0 && s3.sw % 2 == 0 &&
-                         6 * (s3.sw + 2) <= 512 && s3.sw + 2 > 16 &&
-                         lh_[c.level + 1] == H / 2 && lw_[c.level + 1] == W / 2;
-    }
     S.base_lo.assign(bufs_.size(), nullptr);
     for (size_t i = 0; i < bufs_.size(); ++i) {
         S.mem.push_back(std::make_unique<DevBuf>());
@@ -656,16 +671,12 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
         const bool use3 = !c.from_image;
         S.use3[ci] = use3;
         OPK_CHECK_ARG(use3 || c.w.ptr != nullptr, c.info.name + ": weights not set");
-        if (use3) {
-            // (conv3w8's 64-output tile: decided from the destinations as launch_conv3 decides)
-            const bool w8 = w8_eligible(c);
-            const Conv3Shape s3 = conv3_shape(n, H, W, c.info.cout, c.info.k, border_, w8);
-            a.sw = s3.sw;
-            a.nstrips = s3.nstrips;
+        if (use3) {   // (the launchers plan again from these arguments and hold sw / nstrips against it)
+            a.sw = S.conv[ci].sw;
+            a.nstrips = S.conv[ci].nstrips;
+            a.small = S.conv[ci].family == Conv3Family::conv3s;
             a.sink = sink;
-            // GRID_CUS (opk_dev_set, dev): persistent grids of fewer CUs, e.g. two pipelines on
-            // concurrent streams sharing the chip
-            a.cus = std::min(cus_, std::max(1, dev_switch("GRID_CUS", cus_)));
+            a.cus = cus;
         }
         a.w = static_cast<const uint16_t*>(use3 ? c.w3.ptr : c.w.ptr);
         a.bias = static_cast<const float*>(c.bias.ptr);
@@ -701,17 +712,6 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
             a.out32 = S.out32;
             a.out32_c = out_c_;
             a.out32_coff = c.out32_coff;
-        }
-        // small-batch mode: conv3s tiles where conv3_shape's leave most of the chip idle
-        if (use3 && !a.pool) {
-            const Conv3sShape ss = small_pick((int)ci, n, H, W, a.cus, S.fused1);
-            if (ss.ok) {
-                ConvArgs t = a;
-                t.small = 1;
-                t.sw = ss.sw;
-                t.nstrips = ss.nstrips;
-                if (conv3s_supported(t)) a = t;
-            }
         }
     }
     return &S;
@@ -843,46 +843,29 @@ void NetHip::forward_launches(ShapePlan& S, const float* input, int n, int h, in
 // takes a run of whole frames, its pointers moved to the run's first frame -- the positions just
 // before and after a run are frame borders, zero like the guards of a whole-batch launch.
 //
-// Runs are sized evenly (ceil(frames / runs) frames each), and each run takes the strip geometry
-// conv3_shape chooses for ITS frame count: the planner's sw / nstrips were chosen for the whole
-// batch, and a run with fewer tiles may fall into another tile branch (another halo, so another
-// strip count) -- launch_conv3 requires the geometry of its own frame count.
-static bool conv3_run_fits(const ConvArgs& a, int frames, int ks, int B)
-{
-    const Conv3Shape s = conv3_shape(frames, a.H, a.W, a.cout, ks, B, conv3_w8_eligible(a));
-    const long total = (long)frames * s.nstrips * (a.H + 2 * B) * (s.sw + 2 * B);
-    return total + s.bm + (long)(ks - 1) * (s.sw + 2 * B + 1) < (1L << 24);
-}
-
+// Runs are sized evenly (conv3_run_frames: ceil(frames / runs) frames each), and each run takes the
+// plan of ITS frame count: the planner's sw / nstrips were chosen for the whole batch, and a run
+// with fewer tiles may fall into another tile branch (another halo, so another strip count) --
+// launch_conv3 requires the geometry of its own frame count.
 static void launch_conv3_frames(const ConvArgs& a, hipStream_t st)
 {
     const int B = a.border > 0 ? a.border : 1;
-    const int ks = a.ntaps == 49 ? 7 : (a.ntaps == 9 ? 3 : 1);
-    if (a.small) {   // planned on conv3s tiles (whole batch: conv3s_supported checked its range)
-        launch_conv3s(a, st);
-        return;
-    }
-    if (conv3_run_fits(a, a.frames, ks, B)) {
+    Conv3Query q = conv3_query(a);
+    const int run = conv3_run_frames(q);
+    if (run == a.frames) {
         launch_conv3(a, st);
         return;
     }
-    int runs = 2;
-    for (;; ++runs) {   // the fewest even runs whose every run fits (a run of 1 frame always does)
-        const int run = (a.frames + runs - 1) / runs;
-        const int last = a.frames - ((a.frames + run - 1) / run - 1) * run;
-        if (conv3_run_fits(a, run, ks, B) && conv3_run_fits(a, last, ks, B)) break;
-        OPK_CHECK_ARG(run > 1, "launch_conv3_frames: one frame exceeds a launch's position range");
-    }
-    const int run = (a.frames + runs - 1) / runs;
     const size_t frame_pos = (size_t)(a.H + 2 * B) * (a.W + 2 * B);   // padded image positions
     // a pooled destination (conv3w8 POOL epilogue) holds the pooled padded image per frame
     const size_t dst_pos = a.pool ? (size_t)(a.H / 2 + 2 * B) * (a.W / 2 + 2 * B) : frame_pos;
     for (int f0 = 0; f0 < a.frames; f0 += run) {
         ConvArgs b = a;
         b.frames = std::min(run, a.frames - f0);
-        const Conv3Shape sb = conv3_shape(b.frames, a.H, a.W, a.cout, ks, B, conv3_w8_eligible(a));
-        b.sw = sb.sw;
-        b.nstrips = sb.nstrips;
+        q.frames = b.frames;
+        const Conv3Plan pb = conv3_plan(q);
+        b.sw = pb.sw;
+        b.nstrips = pb.nstrips;
         b.M = b.frames * a.H * (a.W + 2 * B);
         b.in = a.in + f0 * frame_pos * a.in_cs;
         if (a.in_lo) b.in_lo = a.in_lo + f0 * frame_pos * a.in_cs;

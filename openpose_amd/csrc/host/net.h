@@ -30,16 +30,21 @@ public:
     static constexpr int kPrecisionFp16 = 0, kPrecisionSplit = 1;
     void set_precision(int precision);
     int precision() const { return precision_; }
-    // Small-batch mode (off by default): 3x3 convs whose conv3_shape geometry gives fewer
-    // workgroups than the chip has CUs run on conv3s tiles (conv3s_pick, conv.h) -- the same
+    // Small-batch mode (off by default): 3x3 convs whose product geometry gives fewer
+    // workgroups than the chip has CUs run on conv3s tiles (conv3_plan, conv.h) -- the same
     // bits, more of the chip busy when a forward is a frame or a few.  Re-plans the shapes.
     void set_small_batch(bool on);
     bool small_batch() const { return small_batch_; }
-    // host-only: the GEMM tile, fill measure (conv3_fill) and kernel family (small: conv3s) the
-    // planner picks for conv `index` of an n x h x w forward on a chip of cus compute units
-    // (the image conv: zeros)
+    // host-only: the GEMM tile, fill measure (Conv3Plan::workgroups) and kernel family (small:
+    // conv3s) the planner picks for conv `index` of an n x h x w forward on a chip of cus compute
+    // units (the image conv: zeros)
     void conv_plan(int index, int n, int h, int w, int cus, int* bm, int* bn, int* workgroups,
                    int* small) const;
+    // host-only: the launch-log name prefix (Conv3Plan::name) of every launch such a forward
+    // makes for conv `index`, in launch order: one per frame run; a conv inside conv1_fused_kernel
+    // or conv_head_kernel gives that kernel's name on the unit's first conv and nothing on the
+    // others; the image conv gives conv_image_kernel
+    std::vector<std::string> conv_kernels(int index, int n, int h, int w, int cus) const;
     bool ready() const;
     // caffe::Net::CopyTrainedLayersFrom (netCaffe.cpp:165,185): weights, bias and PReLU slopes of
     // every conv named in the file (shapes checked as Caffe does); layers the net does not have
@@ -119,20 +124,28 @@ private:
         std::vector<float> hw, hb, hs;   // host copies of the weights (re-packed per precision)
     };
     bool fused1_at(int h, int w) const;            // conv1_fused_kernel runs at this input size
-    bool w8_eligible(const ConvPlan& c) const;     // conv3_w8_eligible of the conv's destinations
-    // the conv3s geometry of conv ci at n x H x W (its level's size), ok == false: conv3_shape's
-    Conv3sShape small_pick(int ci, int n, int H, int W, int cus, bool fused1) const;
     void pack(ConvPlan& c);   // device layouts of one conv's weights for the current precision
     struct PoolPlan { int in_buf, out_buf, level_in, channels; };
     struct Step { bool conv; int idx; };
 
+    // what runs for one input shape on a chip of cus compute units: decided on the host, before
+    // any device memory exists (dispatch())
+    struct Dispatch {
+        std::vector<int> lh, lw;       // size of every pooling level
+        bool split = false;            // planned for kPrecisionSplit: every buffer has a lo twin
+        bool fused1 = false;           // conv1_fused_kernel runs for this shape
+        bool fusedh = false;           // conv_head_kernel runs the fused head pairs
+        std::vector<char> poolfused;   // per pool: run inside its conv's epilogue (conv3w8 POOL)
+        std::vector<Conv3Query> query; // per conv (not the image conv): the whole batch's query
+        std::vector<Conv3Plan> conv;   // ... and its plan
+    };
+    Dispatch dispatch(int n, int h, int w, int cus) const;
+
     // shape-dependent state of one input shape
-    struct ShapePlan {
+    struct ShapePlan : Dispatch {
         int n = 0, h = 0, w = 0;
-        std::vector<int> lh, lw;
         std::vector<std::unique_ptr<DevBuf>> mem;
         std::vector<uint16_t*> base;   // first position of each buffer (past its head guard)
-        bool split = false;            // planned for kPrecisionSplit: every buffer has a lo twin
         std::vector<std::unique_ptr<DevBuf>> mem_lo;
         std::vector<uint16_t*> base_lo;
         DevBuf out_mem, out_mem_alt;
@@ -140,9 +153,6 @@ private:
         float* out32_alt = nullptr;    // the second output buffer (select_output)
         bool alt = false;              // forwards write out32_alt
         float* out() const { return alt ? out32_alt : out32; }
-        bool fused1 = false;           // conv1_fused_kernel runs for this shape
-        bool fusedh = false;           // conv_head_kernel runs the fused head pairs
-        std::vector<char> poolfused;   // per pool: run inside its conv's epilogue (conv3w8 POOL)
         std::vector<ConvArgs> args;    // per conv
         std::vector<char> use3;        // per conv: launch conv3
     };

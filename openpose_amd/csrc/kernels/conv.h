@@ -34,7 +34,7 @@ struct ConvArgs {
     int dst_cs[kConvMaxDst], dst_coff[kConvMaxDst];
     float* out32;         // optional NCHW fp32 [frames][out32_c][H][W]
     int out32_c, out32_coff;
-    int sw, nstrips;      // conv3 only: strip width and count (conv3_shape)
+    int sw, nstrips;      // conv3 only: strip width and count (conv3_plan)
     float rcp[3];         // conv3 only, set by launch_conv3: 1/((H+2)(sw+2)), 1/(sw+2), 1/nstrips
     int wide;             // conv3 only, set by launch_conv3: 16-byte epilogue stores allowed (CONV3_WIDE)
     int prio;             // conv3 persistent: s_setprio(1) around each unit's MFMAs (CONV3P_PRIO)
@@ -47,7 +47,7 @@ struct ConvArgs {
     int bufst;            // conv3w: one destination whose extent is < 2^31 bytes -- epilogue stores
                           // through a buffer resource (set by launch_conv3w)
     int pool;             // conv3w8: 2x2/2 max pool fused into the epilogue; dst[0] is the pooled
-                          // padded image [frames][H/2+2][W/2+2][cs] (conv3w8_pool_supported)
+                          // padded image [frames][H/2+2][W/2+2][cs] (Conv3Plan::pool)
     int nbx;              // conv3w8, several n-blocks: XCD x computes n-block x % NB only, so an
                           // XCD's L2 holds one n-block's weights (set by launch_conv3w8)
     // Split precision (NetHip precision OPK_PRECISION_SPLIT; conv3_kernel only): every activation
@@ -68,7 +68,7 @@ struct ConvArgs {
     const uint16_t* in_lo;
     uint16_t* dst_lo[kConvMaxDst];
     float wscale;
-    int small;            // planned on conv3s tiles (NetHip small-batch mode): sw / nstrips are conv3s_shape's
+    int small;            // planned on conv3s tiles (NetHip small-batch mode): sw / nstrips are the conv3s plan's
     int pbn;              // conv3s only, set by launch_conv3s: the n-block of the weight packing
 };
 // the product of a split virtual chunk (3c + k) that reads w_lo: k = 0 (the order above; dev A/B
@@ -81,60 +81,100 @@ struct ConvArgs {
 // conv3.hip: 7x7, 3x3 and 1x1, input halo staged once per 32-channel chunk over a "virtual image" of
 // column strips (sw interior columns each).  Tile BM x BN = 256 x 128 / 96 (<= 80 KB LDS, two
 // workgroups per CU, or 136 KB, one), 512 x 64 for cout <= 64; optional fp32 NCHW output (out32).
-// Weights packed [cout_pad/BN][cin_pad/32][ky][kx][BN][32] (BN = conv3_shape(...).bn).  Reads padded positions down to -1
+// Weights packed [cout_pad/BN][cin_pad/32][ky][kx][BN][32] (BN = conv3_pack_bn).  Reads padded positions down to -1
 // and the whole row past the last one: buffers carry zeroed guards (kConvGuardTail positions).
 constexpr int kConvGuardTail = 1024;   // positions
 constexpr size_t kConv3SinkBytes = (size_t)1024 * 1024 * 16;   // 1024 lanes x 1024 workgroups x 16 B
-struct Conv3Shape {
-    int ks;                       // 7, 3 or 1
-    int border;                   // zero border of the net's padded images
-    int bm, bn, hr, tapu, minb;   // tile, halo rows, taps per K unit, workgroups per CU
-    int nw;                       // waves per workgroup
-    int sw, nstrips;
-    bool persist;                 // 16-wave tiles: persistent kernel (conv3p) when the launch allows
-};
-// w8: the conv may run on conv3w8 (conv3_w8_eligible): 64-output 3x3 layers of >= 768 tiles then
-// take the persistent 512-position geometry of the 8-wave kernel -- unless its strip would be 16
-// virtual columns or narrower (conv3w8_supported needs more): those keep the 8-wave tiles
-Conv3Shape conv3_shape(int frames, int H, int W, int cout, int ks, int border = 1, bool w8 = false);
-// a 64-output 3x3 conv that conv3w8's BN = 64 instantiation can run (one aligned destination, no
-// fp32 output, a persistent sink): the planner and the launchers decide the same way from it
-bool conv3_w8_eligible(int cout, int ntaps, int ndst, const int* dst_cs, const int* dst_coff, bool out32);
-inline bool conv3_w8_eligible(const ConvArgs& a)
+// the tile of the persistent kernels (conv3p, conv3w, conv3w8): positions and halo rows (the
+// kernels keep bias / slopes in LDS: 688 halo rows where the 16-wave conv3_kernel has 704)
+constexpr int kConvPersistBM = 512, kConvPersistHR = 688;
+
+// ---- conv_plan.cpp: the one decider of which kernel runs a conv, on which tile, strips and grid --
+// Plain host code (no HIP calls): NetHip's planner, its frame runs, the launchers below,
+// opk_net_conv_plan and opk_net_conv_kernels all ask conv3_plan and nothing else decides.
+//
+// Positions are decoded by float-reciprocal division in the kernels (Strips::map), exact below
+// 2^24: a launch's last position (tile and halo overhang included) must fit
+constexpr long kConvMaxPositions = 1L << 24;
+inline bool conv_positions_fit(long last) { return last < kConvMaxPositions; }
+// epilogue stores through a buffer resource: positions x channel stride of the destination (guards
+// included) within the 31-bit offsets of the raw buffer range check
+inline bool conv_bufst_fits(int frames, int Hp, int Wp, int cs)
 {
-    return a.sink && a.cus > 0 && conv3_w8_eligible(a.cout, a.ntaps, a.ndst, a.dst_cs, a.dst_coff, a.out32 != nullptr);
+    return ((long)frames * Hp * Wp + kConvGuardTail) * cs * 2 < (1L << 31) - 4096;
 }
+// n-block of conv3's weight packing (cout only -- and, for 1x1 convs, the CONV1_TILE switch)
+int conv3_pack_bn(int cout, int ks);
+
+enum class Conv3Family { conv3, conv3p, conv3w, conv3w8, conv3s };
+
+// what the decision depends on (no pointers: fillable before any device memory exists)
+struct Conv3Query {
+    int frames, H, W, cout, cin_pad, ntaps;
+    int border;                   // zero border of the net's padded images (<= 0 means 1)
+    int ndst, dst_cs[kConvMaxDst], dst_coff[kConvMaxDst];   // (pool requested: the pooled image's)
+    bool out32;                   // an fp32 NCHW output
+    bool split;
+    bool pool;                    // 2x2/2 max pool in the epilogue requested
+    bool small;                   // small-batch tiles requested (NetHip small-batch mode)
+    bool sink;                    // scratch for the persistent kernels' masked stores
+    int cus;                      // compute units; 0: no persistent kernel
+};
+Conv3Query conv3_query(const ConvArgs& a);
+
+struct Conv3Plan {
+    Conv3Family family;
+    // template parameters of the instantiation (those the geometry fixes)
+    int bm, bn, hr, tapu, minb, ks, nw;
+    int nb;                       // conv3w8: n-blocks (cout / 128)
+    int pbn;                      // n-block of the weight packing (conv3s reads conv3's packing)
+    bool pool;                    // conv3w8 POOL epilogue (false though requested: not supported)
+    bool split;
+    int sw, nstrips, VW;          // strip width and count, virtual row VW = sw + 2 border
+    long total;                   // virtual positions: frames * nstrips * (H + 2 border) * VW
+    long grid;                    // workgroups launched
+    // the planner's measure of how far the geometry fills the chip: tiles of the GEMM's
+    // M = frames * H * (W + 2 border) positions times n-blocks (the grid also covers the border
+    // rows and the strips' shared columns: a few per cent more; persistent grids stop at cus)
+    long workgroups;
+    bool fits;                    // conv_positions_fit: false -> fewer frames per launch (conv3_run_frames)
+    float rcp[3];                 // 1/((H + 2B) VW), 1/VW, 1/nstrips (ConvArgs::rcp)
+    // launch-log name: the whole instantiation for conv3_kernel / conv3s_kernel, up to the
+    // parameters the plan fixes for the persistent kernels ("conv3w8_kernel<BN,NB,POOL")
+    char name[64];
+};
+// Every decision switch is read here (opk_dev_set; per call, so tests compare variants in one
+// process): CONV3_SMALL, CONV3_W16, CONV3_PERSIST, CONV1_TILE, CONV1_N64W16, CONV3W8_64, SPLIT_W8,
+// CONV3W8N, CONV3W (0 / not), CONV3W8, CONV3S_MAX.  Throws for sizes no kernel covers.
+// only: a probe tool's choice among the persistent kernels of a conv that supports it (-1: the
+// product rule); plan.family differs from it when the conv does not.
+Conv3Plan conv3_plan(const Conv3Query& q, int only = -1);
+// frames per launch: q.frames when the plan fits a launch's position range, else the even run
+// size (ceil(frames / runs), fewest runs) at which every run -- planned for its own frame count --
+// fits
+int conv3_run_frames(const Conv3Query& q);
+// the small-batch rule: conv3s when the product geometry gives fewer than cus workgroups and
+// conv3s supports the conv and gives more, but no more than kConv3sMaxPerCu per CU (measured: the
+// 64 x 32 tile is level with the 256-position tiles at 2.8 workgroups per CU and 1.8x slower at 5.7)
+constexpr int kConv3sMaxPerCu = 4;
+// a.sw / a.nstrips checked against the plan; border, rcp and pbn set from it
+ConvArgs conv3_planned_args(const ConvArgs& a, const Conv3Plan& p);
+
+// launch-log names of the other conv kernels a net's conv can run in (the launchers log them with
+// their template arguments; opk_net_conv_kernels reports the bare names)
+constexpr char kConvImageKernel[] = "conv_image_kernel";
+constexpr char kConv1FusedKernel[] = "conv1_fused_kernel";
+constexpr char kConvHeadKernel[] = "conv_head_kernel";
+
+// conv3.hip: the public entry -- plans the conv and launches what the plan says
 void launch_conv3(const ConvArgs& a, hipStream_t stream);
 // conv3w.hip: the persistent 512 x {128, 96} 3x3 variant with one mid-unit barrier per K unit
-// (launched by launch_conv3 for single-n-block layers on the persistent path)
-bool conv3w_supported(const ConvArgs& a);
-void launch_conv3w(const ConvArgs& a, hipStream_t stream);
+void launch_conv3w(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
 // conv3w8.hip: the same tile with 8 waves of 64 x BN (fewer LDS fragment reads per MFMA)
-bool conv3w8_supported(const ConvArgs& a);
-bool conv3w8_pool_supported(const ConvArgs& a);
-void launch_conv3w8(const ConvArgs& a, hipStream_t stream);
+void launch_conv3w8(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
 // conv3s.hip: 3x3 / border 1 convs on small tiles (64 x 32 or 128 x 64, 4 waves), bit-identical to
-// the kernels above, for forwards too small to fill the chip with conv3_shape's tiles.
-// conv3_fill / Conv3sShape::workgroups: the planner's measure of how far a geometry fills the chip,
-// tiles of the GEMM's M = frames * H * (W + 2) positions times n-blocks (the launched grid also
-// covers the border rows and the strips' shared columns: a few per cent more).
-struct Conv3sShape {
-    bool ok;                 // false: not supported (the conv keeps conv3_shape's geometry)
-    int bm, bn, hr, tapu;    // tile, halo rows, taps per K unit
-    int pbn;                 // n-block of the weight packing (conv3_shape's bn)
-    int sw, nstrips;
-    long workgroups, grid;   // fill measure; workgroups launched
-};
-long conv3_fill(const Conv3Shape& s, int frames, int H, int W, int cout);
-Conv3sShape conv3s_shape(int frames, int H, int W, int cout, int border, int cus);
-// the small-batch rule (planner, launcher and opk_net_conv_plan): ok when conv3_shape's geometry
-// (w8 as there) gives fewer than cus workgroups and conv3s supports the conv and gives more, but
-// no more than kConv3sMaxPerCu per CU (measured: the 64 x 32 tile is level with conv3_shape's at
-// 2.8 workgroups per CU and 1.8x slower at 5.7)
-constexpr int kConv3sMaxPerCu = 4;
-Conv3sShape conv3s_pick(int frames, int H, int W, int cout, int border, int cus, bool w8);
-bool conv3s_supported(const ConvArgs& a);
-void launch_conv3s(const ConvArgs& a, hipStream_t stream);
+// the kernels above, for forwards too small to fill the chip with the tiles above
+void launch_conv3s(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
 
 // conv_head.hip: Mconv6 (1x1, n1 = 256 / 512 outputs, act6) -> Mconv7 (1x1, n2 <= 64 outputs) in
 // one kernel; the Mconv6 activations never leave the chip.  Input / outputs as ConvArgs (padded

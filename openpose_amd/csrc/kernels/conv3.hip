@@ -412,7 +412,7 @@ void conv3_kernel(const ConvArgs a)
 // one 16-byte store, plus one 8-byte store per odd last fragment (lanes of border positions write
 // to a scratch "sink"), S = MF*(NF/2 + NF%2)*ndst.
 
-constexpr int kP_BM = 512, kP_HR = 688, kP_NW = 16;
+constexpr int kP_BM = kConvPersistBM, kP_HR = kConvPersistHR, kP_NW = 16;
 
 // LDS fragment reads with explicit counters (ASMR): the compiler streams one fragment at a time
 // behind s_waitcnt lgkmcnt(0) at the 128-VGPR budget (one LDS round trip per 4 MFMAs per wave);
@@ -727,247 +727,74 @@ __global__ __launch_bounds__(64 * kP_NW, 1) void conv3p_kernel(const ConvArgs a)
 
 }  // namespace
 
-bool conv3_w8_eligible(int cout, int ntaps, int ndst, const int* dst_cs, const int* dst_coff, bool out32)
-{
-    return cout == 64 && ntaps == 9 && ndst == 1 && !out32 && ((dst_cs[0] | dst_coff[0]) & 7) == 0 &&
-           dev_switch("CONV3W8_64", 1) != 0;
-}
-
-Conv3Shape conv3_shape(int frames, int H, int W, int cout, int ks, int border, bool w8)
-{
-    // variant switches (opk_dev_set; read per call so tests can compare variants in one process):
-    // CONV3_SMALL=0 -> no two-per-CU tiles, CONV3_W16=0 -> no 16-wave tiles,
-    // CONV3_PERSIST=0 -> 16-wave tiles without the persistent kernel
-    const bool small = dev_switch("CONV3_SMALL", 1) != 0;
-    const int big16 = dev_switch("CONV3_W16", 1);
-    OPK_CHECK_ARG(ks == 1 || ks == 3 || ks == 7, "conv3: 1x1, 3x3 or 7x7");
-    OPK_CHECK_ARG(border >= 1 && border >= ks / 2, "conv3: the zero border must cover the pad");
-    Conv3Shape s;
-    s.ks = ks;
-    s.border = border;
-    s.persist = false;
-    s.bn = cout <= 64 ? 64 : (cout <= 96 ? 96 : 128);
-    if (ks == 1) {   // no halo: small LDS (three tile slots), two workgroups per CU
-        s.nw = 8;
-        s.bm = 256;
-        s.hr = s.bm;
-        s.tapu = 1;
-        s.minb = 2;
-        s.nstrips = 1;
-        s.sw = W;
-        // dev A/B: CONV1_TILE=1 -> 512x128 tiles of 16 waves, 2 -> 256x256 tiles of 16 waves
-        // (cout % 256 == 0): fewer tile rows staged per MFMA than 256x128
-        // (default 2: measured -10..-20 % on the 384->512 and 288->256 layers)
-        const int t1 = dev_switch("CONV1_TILE", 2);
-        if (t1 == 1 && s.bn == 128) {
-            s.bm = 512; s.hr = 512; s.nw = 16; s.minb = 1;
-        } else if (t1 == 2 && cout % 256 == 0) {
-            s.bn = 256; s.nw = 16; s.minb = 1;
-        } else if (s.bn == 64 && dev_switch("CONV1_N64W16", 0) != 0) {   // dev A/B: 512x64, 16 waves
-            s.bm = 512; s.hr = 512; s.nw = 16; s.minb = 1;
-        }
-        return s;
-    }
-    s.nw = 8;
-    if (ks == 7) {   // 7x7 (COCO / MPI / face / hand stages): single-tap units, 1024-row halo
-        s.bm = 256; s.hr = 1024; s.tapu = 1; s.minb = 1;
-    } else {
-        // two workgroups per CU pay off once every CU gets at least two 256-position tiles
-        // (measured: +10-17 % on the 92x164 / 184x328 / 512-channel layers, -20 % at one tile per
-        // CU)
-        const long tiles = ((long)frames * (H + 2 * border) * (W + 2 * border) / 256) *
-                           ((cout + s.bn - 1) / s.bn);
-        // conv3w8 needs strips of more than 16 virtual columns (conv3w8_supported): a narrower
-        // 64-output layer is not taken there and keeps conv3_kernel's 8-wave geometry.  Decided
-        // here, from the strip the persistent halo would give, so that the planner, the frame
-        // runs and launch_conv3 (all callers of this function) agree
-        if (w8 && s.bn == 64) {
-            const int pstrip = (kP_HR - kP_BM - (ks - 1)) / (ks - 1) - 2 * border;
-            const int pn = pstrip > 0 ? (W + pstrip - 1) / pstrip : 1;
-            if ((W + pn - 1) / pn + 2 * border <= 16) w8 = false;
-        }
-        // (measured, round 1: 4-wave 256x128 two-per-CU tiles and 8-wave 512x128 tiles of 128x64
-        // wave tiles were both slower than these on every BODY_25 layer)
-        if ((s.bn != 64 || w8) && big16 && tiles >= 3 * 256) {   // 512 x {128,96} tiles, 16 waves
-            // (64 outputs: only for conv3w8's 8 waves of 64 x 64, conv3_w8_eligible)
-            s.persist = dev_switch("CONV3_PERSIST", 1) != 0;
-            // the persistent kernel keeps bias/slopes in LDS: 688 halo rows
-            s.bm = 512; s.hr = s.persist ? kP_HR : 704; s.tapu = 3; s.minb = 1; s.nw = 16;
-        } else if (small && tiles >= 2 * 256) {   // <= 80 KB of LDS
-            s.bm = 256; s.hr = 448; s.tapu = 1; s.minb = 2;
-        } else if (s.bn != 64) {
-            s.bm = 256; s.hr = 512; s.tapu = 3; s.minb = 1;
-        } else {
-            s.bm = 512; s.hr = 768; s.tapu = 3; s.minb = 1;
-        }
-    }
-    // halo: BM + (ks - 1) * (VW + 1) rows, VW = sw + 2 * border
-    const int max_vw = (s.hr - s.bm - (ks - 1)) / (ks - 1);
-    const int max_strip = max_vw - 2 * border;
-    OPK_CHECK_ARG(max_strip >= 8, "conv3: border too wide for the halo");
-    s.nstrips = (W + max_strip - 1) / max_strip;
-    s.sw = (W + s.nstrips - 1) / s.nstrips;
-    return s;
-}
-
+// The public entry: plans the conv (conv_plan.cpp decides kernel, tile, strips and grid) and
+// launches what the plan says.
+// (a Winograd F(2,3)-along-x variant of the persistent kernel measured 15-50 % slower on every
+// BODY_25 layer -- LDS-read bound: 4 accumulators per output pair halve the wave tile, doubling
+// the fragment reads per MFMA; removed, source and numbers in profiles/round3/wino/)
 void launch_conv3(const ConvArgs& args, hipStream_t stream)
 {
-    ConvArgs a = args;   // + the reciprocals of the strip geometry (Strips::map, kernel arguments)
-    if (a.border <= 0) a.border = 1;
+    const Conv3Plan p = conv3_plan(conv3_query(args));
+    ConvArgs a = args;
     a.wide = dev_switch("CONV3_WIDE", 1);
     a.prio = dev_switch("CONV3P_PRIO", 0);
-    const int B = a.border;
-    a.rcp[0] = (float)(1.0 / ((double)(a.H + 2 * B) * (a.sw + 2 * B)));
-    a.rcp[1] = (float)(1.0 / (double)(a.sw + 2 * B));
-    a.rcp[2] = (float)(1.0 / (double)(a.nstrips > 0 ? a.nstrips : 1));
-    const int ks = a.ntaps == 49 ? 7 : (a.ntaps == 9 ? 3 : 1);
-    OPK_CHECK_ARG((a.ntaps == 49 || a.ntaps == 9 || a.ntaps == 1) && a.cin_pad % 32 == 0 &&
-                      a.cin_pad > 0,
-                  "7x7, 3x3 or 1x1, cin_pad % 32 == 0");
     OPK_CHECK_ARG(a.in_cs % 8 == 0 && a.in_coff % 8 == 0, "input slice must be 16-byte aligned");
     OPK_CHECK_ARG(a.in_coff + a.cin_pad <= a.in_cs, "input slice exceeds the buffer");
-    OPK_CHECK_ARG(a.M > 0 && a.cout > 0 && a.ndst <= kConvMaxDst, "bad sizes");
-    const bool w8 = conv3_w8_eligible(a);
-    const Conv3Shape s = conv3_shape(a.frames, a.H, a.W, a.cout, ks, B, w8);
-    OPK_CHECK_ARG(a.sw == s.sw && a.nstrips == s.nstrips, "strip geometry differs from conv3_shape");
-    const int VW = s.sw + 2 * B;
-    OPK_CHECK_ARG(ks == 1 || s.bm + (ks - 1) * (VW + 1) <= s.hr, "strip too wide for the halo");
-    const long total = (long)a.frames * s.nstrips * (a.H + 2 * B) * VW;
-    OPK_CHECK_ARG(total + s.bm + (long)(ks - 1) * (VW + 1) < (1L << 24), "too many positions per launch");
-    const int nn = (a.cout + s.bn - 1) / s.bn;
-    const long ntiles = ((total + s.bm - 1) / s.bm) * nn;
-    dim3 grid((unsigned)ntiles);
     bool lo_ok = !a.split || a.in_lo;
     for (int d = 0; d < a.ndst && a.split; ++d) lo_ok = lo_ok && a.dst_lo[d];
     OPK_CHECK_ARG(lo_ok, "split precision: lo twins required");
-    // conv + 2x2 max pool in one persistent kernel (conv3w8.hip POOL epilogue); the planner only
-    // asks for it where conv3w8_pool_supported holds
-    if (a.pool) {
-        OPK_CHECK_ARG(s.nw == 16 && s.persist && VW > 16 && conv3w8_pool_supported(a),
-                      "pool fusion requested for an unsupported conv");
-        launch_conv3w8(a, stream);
-        return;
+    // the planner only asks for the pooled epilogue where the plan has it
+    OPK_CHECK_ARG(!a.pool || p.pool, "pool fusion requested for an unsupported conv");
+    switch (p.family) {
+    case Conv3Family::conv3s: launch_conv3s(a, p, stream); return;
+    case Conv3Family::conv3w: launch_conv3w(a, p, stream); return;
+    case Conv3Family::conv3w8: launch_conv3w8(a, p, stream); return;
+    default: break;
     }
-    // (a Winograd F(2,3)-along-x variant of the persistent kernel measured 15-50 % slower on every
-    // BODY_25 layer -- LDS-read bound: 4 accumulators per output pair halve the wave tile, doubling
-    // the fragment reads per MFMA; removed, source and numbers in profiles/round3/wino/)
-    // several 128-channel n-blocks (the VGG 256 / 512-channel layers): conv3w8 with one n-block
-    // per persistent block (bit-identical; CONV3W8N=0: the 16-wave conv3_kernel)
-    // 64-output layers in the persistent geometry (both precisions): conv3w8's BN = 64 tile
-    if (w8 && s.persist && s.bn == 64) {
-        OPK_CHECK_ARG(s.nw == 16 && VW > 16 && conv3w8_supported(a), "conv3w8<64>: unsupported conv");
-        launch_conv3w8(a, stream);
-        return;
+    a = conv3_planned_args(a, p);
+    bool launched = false;
+    if (p.family == Conv3Family::conv3p) {
+        OPK_CHECK_ARG(p.grid >= 1 && p.grid <= 1024, "persistent grid exceeds the sink");
+        // (measured, round 1: a 32x32x16-MFMA version of this kernel with double-buffered
+        // fragments ran 20 % slower on the 128-channel layers; a pipelined 16x16x32 fragment
+        // schedule spilled at the 128-VGPR budget and ran 4 % slower; the explicit-counter
+        // fragment schedule measured 1.5 % faster over the whole CNN, bit-identical)
+        const bool asmr = dev_switch("CONV3P_ASMR", 1) != 0;
+        // 16-byte epilogue stores (measured in tools/ab_asmr.sh; CONV3P_WIDE=0: dwordx2)
+        const bool wide = !asmr || dev_switch("CONV3P_WIDE", 1) != 0;
+#define OPK3P_TRY(BN_, ASMR_, WIDE_)                                                           \
+    if (!launched && p.bn == BN_ && asmr == ASMR_ && wide == WIDE_) {                          \
+        note_launch("%s,%d,%d>", p.name, (int)ASMR_, (int)WIDE_);                              \
+        hipLaunchKernelGGL((conv3p_kernel<BN_, ASMR_, WIDE_>), dim3((unsigned)p.grid), dim3(1024), 0, \
+                           stream, a);                                                         \
+        launched = true;                                                                       \
     }
-    // split precision: every 512-position 96 / 128 / 256 / 512-channel 3x3 layer on conv3w8's split
-    // instantiation (bit-identical to conv3_kernel's; SPLIT_W8=0: conv3_kernel, A/B) -- its three
-    // times longer K loop is the regime where conv3w8 keeps the MFMA pipe busiest; the rest
-    // (several destinations, the 64-channel full-resolution layer, 1x1 heads) on conv3_kernel
-    if (a.split && s.nw == 16 && s.persist && s.bn != 64 && a.sink && !a.out32 && VW > 16 &&
-        dev_switch("SPLIT_W8", 1) != 0 && conv3w8_supported(a)) {
-        launch_conv3w8(a, stream);
-        return;
-    }
-    if (!a.split && s.nw == 16 && s.persist && nn > 1 && s.bn == 128 && a.sink && !a.out32 && VW > 16 &&
-        dev_switch("CONV3W8N", 1) != 0 && conv3w8_supported(a)) {
-        launch_conv3w8(a, stream);
-        return;
-    }
-    // measured: +3-10 % on the single-n-block layers, 3-8 % slower with 2-4 n-blocks (kept 16-wave)
-    if (!a.split && s.nw == 16 && s.persist && nn == 1 && a.sink && a.cus >= nn && a.cout % s.bn == 0 &&
-        !a.out32 && VW > 16) {
-        bool aligned = true;
-        // 16-byte stores of 8-channel groups
-        for (int d = 0; d < a.ndst; ++d) aligned = aligned && ((a.dst_coff[d] | a.dst_cs[d]) & 7) == 0;
-        // mid-unit-barrier schedule (conv3w.hip, bit-identical; CONV3W=0: conv3p_kernel)
-        if (aligned && nn == 1 && dev_switch("CONV3W", 1) != 0 && conv3w_supported(a)) {
-            // 8 waves of 64 x 128 (conv3w8.hip, bit-identical): 25 % fewer LDS fragment reads,
-            // measured 2-4 % faster from cin 384 up and 4 % slower at cin 128 (tile transitions
-            // weigh more there); CONV3W8=0 disables, 2 forces it for 128 outputs, 3 also for 96
-            const int w8 = dev_switch("CONV3W8", 1);
-            if (w8 != 0 && conv3w8_supported(a) &&
-                ((a.cout == 128 && (a.cin_pad >= 384 || w8 >= 2)) || (a.cout == 96 && w8 == 3))) {
-                launch_conv3w8(a, stream);
-                return;
-            }
-            launch_conv3w(a, stream);
-            return;
-        }
-        if (aligned) {   // one workgroup per CU, n-blocks spread evenly over the grid
-            const long per_n = std::min<long>(a.cus / nn, (ntiles + nn - 1) / nn);
-            const unsigned G = (unsigned)(per_n * nn);
-            OPK_CHECK_ARG(G <= 1024, "persistent grid exceeds the sink");
-            // (measured, round 1: a 32x32x16-MFMA version of this kernel with double-buffered
-            // fragments ran 20 % slower on the 128-channel layers; a pipelined 16x16x32 fragment
-            // schedule spilled at the 128-VGPR budget and ran 4 % slower; the explicit-counter
-            // fragment schedule measured 1.5 % faster over the whole CNN, bit-identical)
-            const bool asmr = dev_switch("CONV3P_ASMR", 1) != 0;
-            // 16-byte epilogue stores (measured in tools/ab_asmr.sh; CONV3P_WIDE=0: dwordx2)
-            const bool wide = dev_switch("CONV3P_WIDE", 1) != 0;
-#define OPK3P_LAUNCH(BN_, ASMR_, WIDE_)                                                        \
-    do {                                                                                       \
-        note_launch("conv3p_kernel<%d,%d,%d>", BN_, (int)ASMR_, (int)WIDE_);                   \
-        hipLaunchKernelGGL((conv3p_kernel<BN_, ASMR_, WIDE_>), dim3(G), dim3(1024), 0, stream, a); \
-    } while (0)
-            if (s.bn == 96) {
-                if (asmr) { if (wide) OPK3P_LAUNCH(96, true, true); else OPK3P_LAUNCH(96, true, false); }
-                else OPK3P_LAUNCH(96, false, true);
-            } else {
-                if (asmr) { if (wide) OPK3P_LAUNCH(128, true, true); else OPK3P_LAUNCH(128, true, false); }
-                else OPK3P_LAUNCH(128, false, true);
-            }
-#undef OPK3P_LAUNCH
-            OPK_LAUNCH_CHECK();
-            return;
-        }
-    }
-#define OPK3_LAUNCH(BM_, BN_, HR_, TAPU_, MINB_, KS_)                                          \
-    do {                                                                                       \
-        note_launch("conv3_kernel<%d,%d,%d,%d,%d,%d%s>", BM_, BN_, HR_, TAPU_, MINB_, KS_,      \
-                    a.split ? ",8,split" : "");                                                \
-        if (a.split)                                                                           \
-            hipLaunchKernelGGL((conv3_kernel<BM_, BN_, HR_, TAPU_, MINB_, KS_, 8, true>), grid,  \
-                               dim3(512), 0, stream, a);                                       \
-        else                                                                                   \
-            hipLaunchKernelGGL((conv3_kernel<BM_, BN_, HR_, TAPU_, MINB_, KS_>), grid, dim3(512), 0, \
-                               stream, a);                                                     \
-    } while (0)
-#define OPK3_LAUNCH16(BM_, BN_, HR_, TAPU_, KS_)                                                \
-    do {                                                                                       \
-        note_launch("conv3_kernel<%d,%d,%d,%d,1,%d,16%s>", BM_, BN_, HR_, TAPU_, KS_,          \
-                    a.split ? ",split" : "");                                                  \
-        if (a.split)                                                                           \
-            hipLaunchKernelGGL((conv3_kernel<BM_, BN_, HR_, TAPU_, 1, KS_, 16, true>), grid,     \
-                               dim3(1024), 0, stream, a);                                      \
-        else                                                                                   \
-            hipLaunchKernelGGL((conv3_kernel<BM_, BN_, HR_, TAPU_, 1, KS_, 16>), grid, dim3(1024), 0, \
-                               stream, a);                                                     \
-    } while (0)
-    if (ks == 7) {
-        if (s.bn == 64) OPK3_LAUNCH(256, 64, 1024, 1, 1, 7);
-        else if (s.bn == 96) OPK3_LAUNCH(256, 96, 1024, 1, 1, 7);
-        else OPK3_LAUNCH(256, 128, 1024, 1, 1, 7);
-    } else if (ks == 1) {
-        if (s.nw == 16 && s.bn == 256) OPK3_LAUNCH16(256, 256, 256, 1, 1);
-        else if (s.nw == 16 && s.bn == 64) OPK3_LAUNCH16(512, 64, 512, 1, 1);
-        else if (s.nw == 16) OPK3_LAUNCH16(512, 128, 512, 1, 1);
-        else if (s.bn == 64) OPK3_LAUNCH(256, 64, 256, 1, 2, 1);
-        else if (s.bn == 96) OPK3_LAUNCH(256, 96, 256, 1, 2, 1);
-        else OPK3_LAUNCH(256, 128, 256, 1, 2, 1);
-    } else if (s.bn == 64) {
-        if (s.minb == 2) OPK3_LAUNCH(256, 64, 448, 1, 2, 3);
-        else OPK3_LAUNCH(512, 64, 768, 3, 1, 3);
-    } else if (s.bn == 96) {
-        if (s.nw == 16) OPK3_LAUNCH16(512, 96, 704, 3, 3);
-        else if (s.minb == 2) OPK3_LAUNCH(256, 96, 448, 1, 2, 3);
-        else OPK3_LAUNCH(256, 96, 512, 3, 1, 3);
+        OPK3P_TRY(96, true, true) OPK3P_TRY(96, true, false) OPK3P_TRY(96, false, true)
+        OPK3P_TRY(128, true, true) OPK3P_TRY(128, true, false) OPK3P_TRY(128, false, true)
+#undef OPK3P_TRY
     } else {
-        if (s.nw == 16) OPK3_LAUNCH16(512, 128, 704, 3, 3);
-        else if (s.minb == 2) OPK3_LAUNCH(256, 128, 448, 1, 2, 3);
-        else OPK3_LAUNCH(256, 128, 512, 3, 1, 3);
+        const dim3 grid((unsigned)p.grid), block(64 * p.nw);
+#define OPK3_TRY(BM_, BN_, HR_, TAPU_, MINB_, KS_, NW_)                                        \
+    if (!launched && p.bm == BM_ && p.bn == BN_ && p.hr == HR_ && p.tapu == TAPU_ &&           \
+        p.minb == MINB_ && p.ks == KS_ && p.nw == NW_) {                                       \
+        note_launch("%s", p.name);                                                             \
+        if (a.split)                                                                           \
+            hipLaunchKernelGGL((conv3_kernel<BM_, BN_, HR_, TAPU_, MINB_, KS_, NW_, true>), grid, \
+                               block, 0, stream, a);                                           \
+        else                                                                                   \
+            hipLaunchKernelGGL((conv3_kernel<BM_, BN_, HR_, TAPU_, MINB_, KS_, NW_>), grid, block, 0, \
+                               stream, a);                                                     \
+        launched = true;                                                                       \
     }
-#undef OPK3_LAUNCH
-#undef OPK3_LAUNCH16
+        OPK3_TRY(256, 64, 1024, 1, 1, 7, 8) OPK3_TRY(256, 96, 1024, 1, 1, 7, 8) OPK3_TRY(256, 128, 1024, 1, 1, 7, 8)
+        OPK3_TRY(256, 256, 256, 1, 1, 1, 16) OPK3_TRY(512, 64, 512, 1, 1, 1, 16) OPK3_TRY(512, 128, 512, 1, 1, 1, 16)
+        OPK3_TRY(256, 64, 256, 1, 2, 1, 8) OPK3_TRY(256, 96, 256, 1, 2, 1, 8) OPK3_TRY(256, 128, 256, 1, 2, 1, 8)
+        OPK3_TRY(256, 64, 448, 1, 2, 3, 8) OPK3_TRY(512, 64, 768, 3, 1, 3, 8)
+        OPK3_TRY(512, 96, 704, 3, 1, 3, 16) OPK3_TRY(256, 96, 448, 1, 2, 3, 8) OPK3_TRY(256, 96, 512, 3, 1, 3, 8)
+        OPK3_TRY(512, 128, 704, 3, 1, 3, 16) OPK3_TRY(256, 128, 448, 1, 2, 3, 8) OPK3_TRY(256, 128, 512, 3, 1, 3, 8)
+#undef OPK3_TRY
+    }
+    OPK_CHECK_ARG(launched, std::string("no instantiation of ") + p.name);
     OPK_LAUNCH_CHECK();
 }
 

@@ -1,6 +1,6 @@
 // conv3s.hip -- small-tile 3x3 convolutions for forwards of a few frames (NetHip small-batch mode).
 //
-// conv3_shape's tiles cover 256 or 512 positions by 64 / 96 / 128 outputs: one BODY_25 frame at
+// conv3_kernel's tiles cover 256 or 512 positions by 64 / 96 / 128 outputs: one BODY_25 frame at
 // 656 x 368 gives the 46 x 82 stage layers 16 workgroups on a 256-CU chip.  conv3s_kernel is
 // conv3_kernel (conv3.hip: the halo of a 32-channel chunk staged once, every tap a constant row
 // shift of it, weights as the MFMA's A operand, epilogue straight from registers) with 4 waves
@@ -9,8 +9,9 @@
 //       128-channel layer is 4 barriers long, its first two units' loads in flight at once),
 //   128 positions x 64 outputs, 3-tap K units (conv3_kernel's schedule; 76 KB of LDS: two
 //       workgroups per CU),
-// chosen by conv3s_shape.  (A third tile, 128 x 128 with single-tap units and two workgroups per
-// CU, measured slower than conv3_shape's tiles wherever the rule picked it; DESIGN.md.)  The weights are read from conv3's packing
+// chosen by conv3_plan (conv_plan.cpp).  (A third tile, 128 x 128 with single-tap units and two
+// workgroups per CU, measured slower than conv3_kernel's tiles wherever the rule picked it;
+// DESIGN.md.)  The weights are read from conv3's packing
 // [cout_pad/PBN][cin_pad/32][ky][kx][PBN][32]: a tile's n-block is the row range
 // [n0 % PBN, n0 % PBN + BN) of every [PBN][32] tap block (BN divides PBN).
 //
@@ -267,112 +268,34 @@ __global__ __launch_bounds__(64 * kS_NW) void conv3s_kernel(const ConvArgs a)
     }
 }
 
-// the tiles: {bm, bn, hr, tapu}
-constexpr int kS_NT = 2;
-constexpr int kS_TILES[kS_NT][4] = {{64, 32, 256, 9}, {128, 64, 320, 3}};
-
-long ceil_div(long a, long b) { return (a + b - 1) / b; }
-
 }  // namespace
 
-long conv3_fill(const Conv3Shape& s, int frames, int H, int W, int cout)
+// Reads: a halo row maps to a padded-image position of [0, frames * (H + 2) * (W + 2)), or --
+// outside the virtual image -- to position -1 (Strips::map): within the zeroed guards.  The last
+// strip's columns past the image (nstrips * sw >= W) are masked by Strips::interior.
+void launch_conv3s(const ConvArgs& args, const Conv3Plan& p, hipStream_t stream)
 {
-    return ceil_div((long)frames * H * (W + 2 * s.border), s.bm) * ceil_div(cout, s.bn);
-}
-
-Conv3sShape conv3s_shape(int frames, int H, int W, int cout, int border, int cus)
-{
-    Conv3sShape best{};
-    if (border != 1 || frames <= 0 || H <= 0 || W <= 0 || cout <= 0) return best;
-    const int pbn = cout <= 64 ? 64 : (cout <= 96 ? 96 : 128);   // conv3_shape's n-block (the packing)
-    // the larger tile where it gives at least a workgroup per two CUs (it stages fewer halo and
-    // weight bytes and reads fewer LDS fragments per MFMA), else the smaller one
-    for (int k = kS_NT - 1; k >= 0; --k) {
-        Conv3sShape s{};
-        s.bm = kS_TILES[k][0];
-        s.bn = kS_TILES[k][1];
-        s.hr = kS_TILES[k][2];
-        s.tapu = kS_TILES[k][3];
-        s.pbn = pbn;
-        if (pbn % s.bn != 0) continue;
-        // halo: BM + 2 (VW + 1) rows, VW = sw + 2
-        const int max_strip = (s.hr - s.bm - 2) / 2 - 2;
-        s.nstrips = (W + max_strip - 1) / max_strip;
-        s.sw = (W + s.nstrips - 1) / s.nstrips;
-        const long total = (long)frames * s.nstrips * (H + 2) * (s.sw + 2);
-        if (total + s.hr >= (1L << 24)) continue;   // 24-bit position arithmetic (Strips::map)
-        s.grid = ceil_div(total, s.bm) * ceil_div(cout, s.bn);
-        s.workgroups = ceil_div((long)frames * H * (W + 2), s.bm) * ceil_div(cout, s.bn);
-        s.ok = true;
-        if (k == 1 && 2 * s.workgroups < cus) {
-            best = s;   // (kept if the smaller tile is unsupported)
-            continue;
-        }
-        return s;
-    }
-    return best;
-}
-
-Conv3sShape conv3s_pick(int frames, int H, int W, int cout, int border, int cus, bool w8)
-{
-    const Conv3Shape s3 = conv3_shape(frames, H, W, cout, 3, border, w8);
-    const long today = conv3_fill(s3, frames, H, W, cout);
-    Conv3sShape s = conv3s_shape(frames, H, W, cout, border, cus);
-    // CONV3S_MAX (opk_dev_set, tuning): no small tiles beyond this many workgroups per CU
-    const long most = (long)std::max(1, dev_switch("CONV3S_MAX", kConv3sMaxPerCu)) * cus;
-    if (!s.ok || today >= cus || s.workgroups <= today || s.workgroups > most) s.ok = false;
-    return s;
-}
-
-bool conv3s_supported(const ConvArgs& a)
-{
-    const int B = a.border <= 0 ? 1 : a.border;
-    if (a.ntaps != 9 || B != 1 || a.pool || a.cin_pad <= 0 || a.cin_pad % 32 != 0) return false;
-    if (a.in_cs % 8 != 0 || a.in_coff % 8 != 0 || a.in_coff + a.cin_pad > a.in_cs) return false;
-    if (a.ndst < 0 || a.ndst > kConvMaxDst || a.cout <= 0 || a.frames <= 0) return false;
-    if (a.split && !a.in_lo) return false;
-    for (int d = 0; d < a.ndst && a.split; ++d)
-        if (!a.dst_lo[d]) return false;
-    return conv3s_shape(a.frames, a.H, a.W, a.cout, B, a.cus > 0 ? a.cus : 1).ok;
-}
-
-void launch_conv3s(const ConvArgs& args, hipStream_t stream)
-{
-    ConvArgs a = args;
-    if (a.border <= 0) a.border = 1;
-    OPK_CHECK_ARG(conv3s_supported(a), "conv3s: unsupported conv");
-    const Conv3sShape s = conv3s_shape(a.frames, a.H, a.W, a.cout, a.border, a.cus > 0 ? a.cus : 1);
-    OPK_CHECK_ARG(a.sw == s.sw && a.nstrips == s.nstrips, "strip geometry differs from conv3s_shape");
-    a.pbn = s.pbn;
-    const int VW = s.sw + 2, Hp = a.H + 2, Wp = a.W + 2;
-    a.rcp[0] = (float)(1.0 / ((double)Hp * VW));
-    a.rcp[1] = (float)(1.0 / (double)VW);
-    a.rcp[2] = (float)(1.0 / (double)s.nstrips);
-    // the halo rows of a tile are the virtual positions [p0 - VW - 1, p0 - VW - 1 + hr): every tap
-    // row of the tile lies in them
-    OPK_CHECK_ARG(s.bm + 2 * (VW + 1) <= s.hr, "strip too wide for the halo");
-    const long total = (long)a.frames * s.nstrips * Hp * VW;
-    OPK_CHECK_ARG(total + s.hr < (1L << 24), "too many positions per launch");
-    // reads: a halo row maps to a padded-image position of [0, frames * Hp * Wp), or -- outside the
-    // virtual image -- to position -1 (Strips::map): within the zeroed guards, W + 3 positions
-    // before the first frame and kConvGuardTail after the last
-    const long lowest = -1, highest = (long)a.frames * Hp * Wp - 1;
-    OPK_CHECK_ARG(lowest >= -(long)(a.W + 3) && highest < (long)a.frames * Hp * Wp + kConvGuardTail,
-                  "halo reads leave the guards");
-    // the last strip's columns past the image (nstrips * sw >= W) are masked by Strips::interior
-    OPK_CHECK_ARG((long)s.nstrips * s.sw >= a.W && (long)(s.nstrips - 1) * s.sw < a.W, "strips do not tile the row");
-    const dim3 grid((unsigned)s.grid), block(64 * kS_NW);
-#define OPK3S_LAUNCH(BM_, BN_, HR_, TAPU_)                                                     \
-    do {                                                                                       \
-        note_launch("conv3s_kernel<%d,%d,%d,%d%s>", BM_, BN_, HR_, TAPU_, a.split ? ",split" : ""); \
+    OPK_CHECK_ARG(p.family == Conv3Family::conv3s && !args.pool, "conv3s: unsupported conv");
+    OPK_CHECK_ARG(args.in_cs % 8 == 0 && args.in_coff % 8 == 0 && args.in_coff + args.cin_pad <= args.in_cs,
+                  "conv3s: input slice unaligned or beyond the buffer");
+    bool lo_ok = !args.split || args.in_lo;
+    for (int d = 0; d < args.ndst && args.split; ++d) lo_ok = lo_ok && args.dst_lo[d];
+    OPK_CHECK_ARG(lo_ok, "conv3s split: lo twins required");
+    const ConvArgs a = conv3_planned_args(args, p);
+    const dim3 grid((unsigned)p.grid), block(64 * kS_NW);
+    bool launched = false;
+#define OPK3S_TRY(BM_, BN_, HR_, TAPU_)                                                        \
+    if (!launched && p.bm == BM_ && p.bn == BN_ && p.hr == HR_ && p.tapu == TAPU_) {           \
+        note_launch("%s", p.name);                                                             \
         if (a.split)                                                                           \
             hipLaunchKernelGGL((conv3s_kernel<BM_, BN_, HR_, TAPU_, true>), grid, block, 0, stream, a); \
         else                                                                                   \
             hipLaunchKernelGGL((conv3s_kernel<BM_, BN_, HR_, TAPU_, false>), grid, block, 0, stream, a); \
-    } while (0)
-    if (s.bm == 64) OPK3S_LAUNCH(64, 32, 256, 9);
-    else OPK3S_LAUNCH(128, 64, 320, 3);
-#undef OPK3S_LAUNCH
+        launched = true;                                                                       \
+    }
+    OPK3S_TRY(64, 32, 256, 9) OPK3S_TRY(128, 64, 320, 3)
+#undef OPK3S_TRY
+    OPK_CHECK_ARG(launched, std::string("no instantiation of ") + p.name);
     OPK_LAUNCH_CHECK();
 }
 

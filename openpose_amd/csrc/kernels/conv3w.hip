@@ -44,7 +44,7 @@ namespace {
 
 using namespace conv3dev;
 
-constexpr int kW_BM = 512, kW_HR = 688, kW_NW = 16;
+constexpr int kW_BM = kConvPersistBM, kW_HR = kConvPersistHR, kW_NW = 16;
 
 #ifdef OPKW_STAMPS   // dev probe (tools/conv3w_probe.hip): per-block phase timestamps of wave 0
 __device__ unsigned long long* opkw_stamps;
@@ -512,47 +512,31 @@ __global__ __launch_bounds__(64 * kW_NW, 1) void conv3w_kernel(const ConvArgs a)
 
 }  // namespace
 
-bool conv3w_supported(const ConvArgs& a)
+void launch_conv3w(const ConvArgs& args, const Conv3Plan& p, hipStream_t stream)
 {
-    bool aligned = true;   // 16-byte stores of 8-channel groups
-    for (int d = 0; d < a.ndst; ++d) aligned = aligned && ((a.dst_coff[d] | a.dst_cs[d]) & 7) == 0;
-    return a.ntaps == 9 && (a.cout == 128 || a.cout == 96) && a.sink && a.cus > 0 && !a.out32 &&
-           aligned && a.sw + 2 * a.border > 16;
-}
-
-void launch_conv3w(const ConvArgs& a, hipStream_t stream)
-{
-    OPK_CHECK_ARG(conv3w_supported(a), "conv3w: 96 / 128 output channels, 3x3, aligned slices");
-    const long total = (long)a.frames * a.nstrips * (a.H + 2 * a.border) * (a.sw + 2 * a.border);
-    const long ntm = (total + kW_BM - 1) / kW_BM;
-    const unsigned G = (unsigned)std::min<long>(a.cus, ntm);
-    OPK_CHECK_ARG(G <= 1024, "persistent grid exceeds the sink");
+    OPK_CHECK_ARG(p.family == Conv3Family::conv3w, "conv3w: 96 / 128 output channels, 3x3, aligned slices");
+    OPK_CHECK_ARG(p.grid >= 1 && p.grid <= 1024, "persistent grid exceeds the sink");
+    ConvArgs b = conv3_planned_args(args, p);
     const bool dma_end = dev_switch("CONV3W", 1) != 2;   // 2: DMA right after the barrier (A/B)
-    // buffer-resource epilogue stores (BUFST=0: pointer stores, A/B): one destination whose
-    // positions x channel stride fit the 31-bit offsets of the raw buffer range check
-    ConvArgs b = a;
-    const long extent = ((long)a.frames * (a.H + 2 * a.border) * (a.W + 2 * a.border) + kConvGuardTail) *
-                        a.dst_cs[0] * 2;
-    b.bufst = a.ndst == 1 && extent < (1L << 31) - 4096 && dev_switch("BUFST", 1) != 0;
+    // buffer-resource epilogue stores (BUFST=0: pointer stores, A/B): one destination
+    b.bufst = b.ndst == 1 && conv_bufst_fits(b.frames, b.H + 2 * b.border, b.W + 2 * b.border, b.dst_cs[0]) &&
+              dev_switch("BUFST", 1) != 0;
     // (the DMA-after-barrier A/B variant only with the select activation)
-#define OPKW_LAUNCH(BN_, DE_, MX_)                                                                 \
-    do {                                                                                          \
-        note_launch("conv3w_kernel<%d,%d,%d,%d>", BN_, (int)DE_, (int)MX_, b.bufst);              \
-        if (b.bufst)                                                                              \
-            hipLaunchKernelGGL((conv3w_kernel<BN_, DE_, MX_, true>), dim3(G), dim3(64 * kW_NW), 0, stream, b); \
-        else                                                                                      \
-            hipLaunchKernelGGL((conv3w_kernel<BN_, DE_, MX_, false>), dim3(G), dim3(64 * kW_NW), 0, stream, b); \
-    } while (0)
-    if (a.cout == 128) {
-        if (!dma_end) OPKW_LAUNCH(128, false, false);
-        else if (a.actmax) OPKW_LAUNCH(128, true, true);
-        else OPKW_LAUNCH(128, true, false);
-    } else {
-        if (!dma_end) OPKW_LAUNCH(96, false, false);
-        else if (a.actmax) OPKW_LAUNCH(96, true, true);
-        else OPKW_LAUNCH(96, true, false);
+    const bool mx = dma_end && b.actmax;
+    bool launched = false;
+#define OPKW_TRY(BN_, DE_, MX_, BS_)                                                               \
+    if (!launched && p.bn == BN_ && dma_end == DE_ && mx == MX_ && (b.bufst != 0) == BS_) {        \
+        note_launch("%s,%d,%d,%d>", p.name, (int)DE_, (int)MX_, (int)BS_);                        \
+        hipLaunchKernelGGL((conv3w_kernel<BN_, DE_, MX_, BS_>), dim3((unsigned)p.grid), dim3(64 * kW_NW), 0, \
+                           stream, b);                                                            \
+        launched = true;                                                                          \
     }
-#undef OPKW_LAUNCH
+#define OPKW_TRY2(BN_, DE_, MX_) OPKW_TRY(BN_, DE_, MX_, true) OPKW_TRY(BN_, DE_, MX_, false)
+    OPKW_TRY2(128, false, false) OPKW_TRY2(128, true, true) OPKW_TRY2(128, true, false)
+    OPKW_TRY2(96, false, false) OPKW_TRY2(96, true, true) OPKW_TRY2(96, true, false)
+#undef OPKW_TRY2
+#undef OPKW_TRY
+    OPK_CHECK_ARG(launched, std::string("no instantiation of ") + p.name);
     OPK_LAUNCH_CHECK();
 }
 

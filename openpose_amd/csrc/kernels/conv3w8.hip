@@ -31,7 +31,7 @@ namespace {
 
 using namespace conv3dev;
 
-constexpr int k8_BM = 512, k8_HR = 688, k8_NW = 8;
+constexpr int k8_BM = kConvPersistBM, k8_HR = kConvPersistHR, k8_NW = 8;
 
 // Unit u+2's DMA right after the mid-unit barrier (a third of a unit more lead) instead of after
 // tap 2: the split 96- and 64-output tiles (measured 3-3.5 % faster per launch, round 6,
@@ -714,84 +714,41 @@ __global__ __launch_bounds__(64 * k8_NW, 1) void conv3w8_kernel(const ConvArgs a
 
 }  // namespace
 
-bool conv3w8_supported(const ConvArgs& a)
+void launch_conv3w8(const ConvArgs& args, const Conv3Plan& p, hipStream_t stream)
 {
-    // one 16-byte store per (fragment pair, destination), 16-byte aligned slices; several
-    // destinations (conv4_4_CPM's five concat slices) wait for every store at a tile's first
-    // mid-unit instead of counting them
-    bool aligned = a.ndst >= 1 && a.ndst <= kConvMaxDst;
-    for (int d = 0; d < a.ndst; ++d) aligned = aligned && ((a.dst_coff[d] | a.dst_cs[d]) & 7) == 0;
-    // 64, 96 or 128 channels, or several 128-channel blocks (the VGG 256 / 512-channel layers)
-    const bool nb_ok = a.cout == 64 || a.cout == 96 || a.cout == 128 || a.cout == 256 || a.cout == 512;
-    return a.ntaps == 9 && nb_ok && a.sink && a.cus > 0 && !a.out32 && aligned &&
-           a.sw + 2 * a.border > 16;
-}
-
-bool conv3w8_pool_supported(const ConvArgs& a)
-{
-    // windows never straddle a strip or a 6-row tile: even sizes, even strips, 1-pixel border;
-    // the pooled image is dst[0] (one destination)
-    return conv3w8_supported(a) && (a.cout % 128 == 0 || a.cout == 64) && a.ndst == 1 && a.border == 1 &&
-           a.H % 2 == 0 && a.W % 2 == 0 && a.sw % 2 == 0 && 6 * (a.sw + 2) <= k8_BM;
-}
-
-void launch_conv3w8(const ConvArgs& a, hipStream_t stream)
-{
-    OPK_CHECK_ARG(conv3w8_supported(a), "conv3w8: 96 or k x 128 output channels, 3x3, one aligned slice");
-    const long total = (long)a.frames * a.nstrips * (a.H + 2 * a.border) * (a.sw + 2 * a.border);
-    const int VW = a.sw + 2 * a.border;
-    const bool pool = a.pool != 0;
-    if (pool)
-        OPK_CHECK_ARG(conv3w8_pool_supported(a), "conv3w8 + pool: even H, W and strips, 64 / 128k outputs, border 1");
-    const long ntm = pool ? (total / VW - 1 + 5) / 6 : (total + k8_BM - 1) / k8_BM;
-    const int nb = a.cout <= 128 ? 1 : a.cout / 128;
-    // a multiple of the n-block count (each block keeps one n-block)
-    const unsigned G = (unsigned)(std::min<long>(a.cus / nb, ntm) * nb);
-    OPK_CHECK_ARG(G >= 1 && G <= 1024, "persistent grid exceeds the sink");
-    // buffer-resource epilogue stores (BUFST=0: pointer stores, A/B): one destination whose
-    // positions x channel stride fit the 31-bit offsets of the raw buffer range check
-    ConvArgs b = a;
-    const long extent = ((long)a.frames * (a.H + 2 * a.border) * (a.W + 2 * a.border) + kConvGuardTail) *
-                        a.dst_cs[0] * 2;
-    const long pextent = ((long)a.frames * (a.H / 2 + 2) * (a.W / 2 + 2) + kConvGuardTail) * a.dst_cs[0] * 2;
-    b.bufst = a.ndst == 1 && (pool ? pextent : extent) < (1L << 31) - 4096 && dev_switch("BUFST", 1) != 0;
+    OPK_CHECK_ARG(p.family == Conv3Family::conv3w8, "conv3w8: 96 or k x 128 output channels, 3x3, one aligned slice");
+    OPK_CHECK_ARG(p.grid >= 1 && p.grid <= 1024, "persistent grid exceeds the sink");
+    OPK_CHECK_ARG((args.pool != 0) == p.pool, "conv3w8 + pool: even H, W and strips, 64 / 128k outputs, border 1");
+    OPK_CHECK_ARG(!args.split || (args.in_lo && args.dst_lo[0]), "conv3w8 split: lo twins");
+    ConvArgs b = conv3_planned_args(args, p);
+    // buffer-resource epilogue stores (BUFST=0: pointer stores, A/B): one destination (pooled:
+    // the pooled padded image)
+    const int Hd = p.pool ? b.H / 2 + 2 : b.H + 2 * b.border, Wd = p.pool ? b.W / 2 + 2 : b.W + 2 * b.border;
+    b.bufst = b.ndst == 1 && conv_bufst_fits(b.frames, Hd, Wd, b.dst_cs[0]) && dev_switch("BUFST", 1) != 0;
     // n-blocks by XCD (W8_NBX=1, dev A/B): measured neutral in both precisions (round 6,
     // profiles/round6/r6c: split 104.0 vs 104.1 ms, fp16 33.6 vs 33.6 ms per 130-frame forward),
     // so the m-tile-major order stays the default
-    b.nbx = nb > 1 && G % 8 == 0 && dev_switch("W8_NBX", 0) != 0;
-#define OPK8_LAUNCH3(BN_, NB_, P_, MX_, SP_)                                                     \
-    do {                                                                                        \
-        note_launch("conv3w8_kernel<%d,%d,%d,%d,%d%s>", BN_, NB_, (int)P_, (int)MX_, b.bufst,     \
-                    SP_ ? ",split" : "");                                                       \
-        if (b.bufst)                                                                            \
-            hipLaunchKernelGGL((conv3w8_kernel<BN_, NB_, P_, MX_, true, SP_>), dim3(G), dim3(64 * k8_NW), 0, stream, b); \
-        else                                                                                    \
-            hipLaunchKernelGGL((conv3w8_kernel<BN_, NB_, P_, MX_, false, SP_>), dim3(G), dim3(64 * k8_NW), 0, stream, b); \
-    } while (0)
-#define OPK8_LAUNCH2(BN_, NB_, P_, MX_)                                                          \
-    do {                                                                                        \
-        if (a.split) OPK8_LAUNCH3(BN_, NB_, P_, MX_, true);                                     \
-        else OPK8_LAUNCH3(BN_, NB_, P_, MX_, false);                                            \
-    } while (0)
-#define OPK8_LAUNCH(BN_, NB_, P_)                                                                \
-    do {                                                                                        \
-        if (a.actmax) OPK8_LAUNCH2(BN_, NB_, P_, true);                                         \
-        else OPK8_LAUNCH2(BN_, NB_, P_, false);                                                 \
-    } while (0)
-    OPK_CHECK_ARG(!a.split || (a.in_lo && a.dst_lo[0]), "conv3w8 split: lo twins");
-    if (pool) {
-        if (nb == 4) OPK8_LAUNCH(128, 4, true);
-        else if (nb == 2) OPK8_LAUNCH(128, 2, true);
-        else if (a.cout == 64) OPK8_LAUNCH(64, 1, true);
-        else OPK8_LAUNCH(128, 1, true);
-    } else if (nb == 4) OPK8_LAUNCH(128, 4, false);
-    else if (nb == 2) OPK8_LAUNCH(128, 2, false);
-    else if (a.cout == 128) OPK8_LAUNCH(128, 1, false);
-    else if (a.cout == 96) OPK8_LAUNCH(96, 1, false);
-    else OPK8_LAUNCH(64, 1, false);
-#undef OPK8_LAUNCH
-#undef OPK8_LAUNCH2
-#undef OPK8_LAUNCH3
+    b.nbx = p.nb > 1 && p.grid % 8 == 0 && dev_switch("W8_NBX", 0) != 0;
+    const bool mx = b.actmax != 0, bs = b.bufst != 0, sp = b.split != 0;
+    bool launched = false;
+#define OPK8_TRY(BN_, NB_, P_, MX_, BS_, SP_)                                                    \
+    if (!launched && p.bn == BN_ && p.nb == NB_ && p.pool == P_ && mx == MX_ && bs == BS_ && sp == SP_) { \
+        note_launch("%s,%d,%d%s>", p.name, (int)MX_, (int)BS_, SP_ ? ",split" : "");             \
+        hipLaunchKernelGGL((conv3w8_kernel<BN_, NB_, P_, MX_, BS_, SP_>), dim3((unsigned)p.grid), \
+                           dim3(64 * k8_NW), 0, stream, b);                                     \
+        launched = true;                                                                        \
+    }
+#define OPK8_TRY3(BN_, NB_, P_, MX_) \
+    OPK8_TRY(BN_, NB_, P_, MX_, true, true) OPK8_TRY(BN_, NB_, P_, MX_, true, false)             \
+    OPK8_TRY(BN_, NB_, P_, MX_, false, true) OPK8_TRY(BN_, NB_, P_, MX_, false, false)
+#define OPK8_TRY2(BN_, NB_, P_) OPK8_TRY3(BN_, NB_, P_, true) OPK8_TRY3(BN_, NB_, P_, false)
+    OPK8_TRY2(128, 4, true) OPK8_TRY2(128, 2, true) OPK8_TRY2(64, 1, true) OPK8_TRY2(128, 1, true)
+    OPK8_TRY2(128, 4, false) OPK8_TRY2(128, 2, false) OPK8_TRY2(128, 1, false) OPK8_TRY2(96, 1, false)
+    OPK8_TRY2(64, 1, false)
+#undef OPK8_TRY2
+#undef OPK8_TRY3
+#undef OPK8_TRY
+    OPK_CHECK_ARG(launched, std::string("no instantiation of ") + p.name);
     OPK_LAUNCH_CHECK();
 }
 

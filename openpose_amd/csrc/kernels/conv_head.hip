@@ -500,7 +500,7 @@ void launch_conv_head(const HeadArgs& a, hipStream_t stream)
     }
     const long total = (long)a.frames * (a.H + 2) * (a.W + 2);
     // phase 3 decodes positions by float-reciprocal division, exact below 2^24 (conv3_dev.h)
-    OPK_CHECK_ARG(total < (1L << 24), "conv_head: too many positions (split the batch)");
+    OPK_CHECK_ARG(conv_positions_fit(total), "conv_head: too many positions (split the batch)");
     const long ntiles = (total + kH_BM - 1) / kH_BM;
     // persistent at N1 = 512 (one 143 KB workgroup per CU: 4-5 % faster than one workgroup per
     // tile); at N1 = 256 two per-tile workgroups share a CU and the persistent grid measured
@@ -512,7 +512,7 @@ void launch_conv_head(const HeadArgs& a, hipStream_t stream)
     const dim3 blk(64 * kH_NW);
 #define OPKH_LAUNCH3(N1_, NF2_, MX_, SP_)                                                       \
     do {                                                                                       \
-        note_launch("conv_head_kernel<%d,%d,%d,%d%s>", N1_, NF2_, (int)persist, (int)MX_, SP_ ? ",split" : ""); \
+        note_launch("%s<%d,%d,%d,%d%s>", kConvHeadKernel, N1_, NF2_, (int)persist, (int)MX_, SP_ ? ",split" : ""); \
         if (persist) hipLaunchKernelGGL((conv_head_kernel<N1_, NF2_, true, MX_, SP_>), dim3(G), blk, 0, stream, a); \
         else hipLaunchKernelGGL((conv_head_kernel<N1_, NF2_, false, MX_, SP_>), dim3(G), blk, 0, stream, a); \
     } while (0)

@@ -258,12 +258,12 @@ void launch_conv_image(const ConvArgs& a, const float* image, hipStream_t stream
     hipLaunchKernelGGL((conv_image_kernel<SP_, WI_, ST_>), dim3((unsigned)blocks), dim3(256), 0, stream, a, image)
     if (a.split) {
         for (int d = 0; d < a.ndst; ++d) OPK_CHECK_ARG(a.dst_lo[d] != nullptr, "conv_image: split needs dst_lo");
-        note_launch("conv_image_kernel<split>");
+        note_launch("%s<split>", kConvImageKernel);
         if (stage) OPKI_LAUNCH(true, true, true);
         else if (wide) OPKI_LAUNCH(true, true, false);
         else OPKI_LAUNCH(true, false, false);
     } else {
-        note_launch("conv_image_kernel");
+        note_launch("%s", kConvImageKernel);
         if (stage) OPKI_LAUNCH(false, true, true);
         else if (wide) OPKI_LAUNCH(false, true, false);
         else OPKI_LAUNCH(false, false, false);

@@ -1,6 +1,6 @@
 // conv3_probe.hip -- dev tool: per-block phase timing of the conv3 halo kernel (s_memtime stamps).
 //
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -o /tmp/conv3_probe tools/conv3_probe.hip
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude -o tools/conv3_probe tools/conv3_probe.hip
 //   conv3_probe [frames H W cin cout iters]
 //
 // Prints, over all blocks of one launch, the mean/min/max shader cycles spent in
@@ -8,6 +8,10 @@
 // plus the kernel's wall time from HIP events.  Inputs are random; only timing matters.
 #define OPK3_STAMPS
 #include "../openpose_amd/csrc/kernels/conv3.hip"
+#include "../openpose_amd/csrc/kernels/conv3s.hip"
+#include "../openpose_amd/csrc/kernels/conv3w.hip"
+#include "../openpose_amd/csrc/kernels/conv3w8.hip"
+#include "../openpose_amd/csrc/kernels/conv_plan.cpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -19,6 +23,7 @@ using namespace opk;
 
 // the library's opk_dev_set table is not linked into this dev tool: variant switches come from
 // OPK_<KEY> environment variables here (tools/probe_run.sh)
+void opk::note_launch(const char*, ...) {}
 int opk::dev_switch(const char* key, int dflt)
 {
     const char* e = std::getenv((std::string("OPK_") + key).c_str());
@@ -93,11 +98,10 @@ int main(int argc, char** argv)
     int cus = 0;
     CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
     a.cus = cus;
-    const Conv3Shape s3 = conv3_shape(frames, H, W, cout, 3);
+    const Conv3Plan s3 = conv3_plan(conv3_query(a));   // (OPK_CONV3_PERSIST=0: conv3_kernel, the stamped one)
     a.sw = s3.sw;
     a.nstrips = s3.nstrips;
-    const long vtot = (long)frames * s3.nstrips * (H + 2) * (s3.sw + 2);
-    const int nblk = (int)(((vtot + s3.bm - 1) / s3.bm) * ((cout + s3.bn - 1) / s3.bn));
+    const int nblk = (int)s3.grid;
     CK(hipMalloc(&dst, (size_t)nblk * 8 * 8));
     CK(hipMemset(dst, 0, (size_t)nblk * 8 * 8));
     CK(hipMemcpyToSymbol(HIP_SYMBOL(opk3_stamps), &dst, sizeof(dst)));

@@ -14,6 +14,7 @@
 #ifdef NOSTAMPS
 #include "../openpose_amd/csrc/kernels/conv3w8.hip"
 #endif
+#include "../openpose_amd/csrc/kernels/conv_plan.cpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -100,10 +101,7 @@ int main(int argc, char** argv)
     CK(hipDeviceGetAttribute(&a.cus, hipDeviceAttributeMultiprocessorCount, 0));
     a.border = 1;
     a.sw = W;          // one strip (W + 2 <= 87 for the 688-row halo)
-    a.nstrips = 1;
-    a.rcp[0] = (float)(1.0 / ((double)(H + 2) * (W + 2)));
-    a.rcp[1] = (float)(1.0 / (double)(W + 2));
-    a.rcp[2] = 1.f;
+    a.nstrips = 1;     // (the launchers hold both against conv3_plan and set the reciprocals)
     const long ntm = (pos + 511) / 512;
     const int G = (int)std::min<long>(a.cus, ntm);
     unsigned long long* dst;
@@ -122,9 +120,9 @@ int main(int argc, char** argv)
     CK(hipEventCreate(&e1));
     auto launch = [&](const ConvArgs& x) {
 #ifdef NOSTAMPS
-        if (variant == 1) { launch_conv3w8(x, 0); return; }
+        if (variant == 1) { launch_conv3w8(x, conv3_plan(conv3_query(x), (int)Conv3Family::conv3w8), 0); return; }
 #endif
-        launch_conv3w(x, 0);
+        launch_conv3w(x, conv3_plan(conv3_query(x), (int)Conv3Family::conv3w), 0);
     };
     CK(hipMemset(dout, 0, out_elems * 2));
     for (int i = 0; i < 5; ++i) launch(a);
@@ -143,7 +141,7 @@ int main(int argc, char** argv)
         CK(hipMemset(dref, 0, out_elems * 2));
         ConvArgs b = a;
         b.dst[0] = dref + head * cout;
-        launch_conv3w(b, 0);
+        launch_conv3w(b, conv3_plan(conv3_query(b), (int)Conv3Family::conv3w), 0);
         CK(hipDeviceSynchronize());
         std::vector<uint16_t> h1(out_elems), h2(out_elems);
         CK(hipMemcpy(h1.data(), dout, out_elems * 2, hipMemcpyDeviceToHost));
