@@ -290,11 +290,13 @@ int opk_net_flops_per_frame(opk_net* net, int h, int w, double* flops);
 #define OPK_PRECISION_FP16 0
 #define OPK_PRECISION_SPLIT 1
 int opk_net_set_precision(opk_net* net, int precision);
-/* Small-batch mode (no reference counterpart).  The default planning tiles every 3x3 conv for the
- * large batches of opk_pose_submit (256 or 512 positions x 64..128 outputs): a forward of one
- * frame, as op::PoseExtractorCaffe::forwardPass runs it, leaves most compute units idle.
- * 0 (default): today's planning.  1: 3x3 layers that would not fill the chip run on conv3s tiles;
- * results are bit-identical either way.  Re-plans the net's shapes. */
+/* Small-batch mode (no reference counterpart).  The default planning tiles every 3x3 and 7x7 conv
+ * for the large batches of opk_pose_submit (256 or 512 positions x 64..128 outputs): a forward of
+ * one frame, as op::PoseExtractorCaffe::forwardPass runs it, or of a few face / hand crops, leaves
+ * most compute units idle.
+ * 0 (default): today's planning.  1: 3x3 layers (any net) and 7x7 layers (the COCO / MPI / face /
+ * hand stages) that would not fill the chip run on conv3s tiles; the 1x1 layers are planned as
+ * without the mode.  Results are bit-identical either way.  Re-plans the net's shapes. */
 int opk_net_set_small_batch(opk_net* net, int enable);   /* other values: OPK_ERR_ARG */
 int opk_net_small_batch(opk_net* net);                    /* 0 / 1, -1 for NULL */
 /* Host-only (works on a device -1 context): the conv geometry the planner picks for conv `index`

@@ -379,9 +379,9 @@ NetHip::Dispatch NetHip::dispatch(int n, int h, int w, int cus) const
         q.split = D.split;
         q.sink = true;
         q.cus = cus;
-        // small-batch mode: 3x3 convs that run as launches of their own (the fused units are
-        // planned as without the mode)
-        q.small = small_batch_ && c.ntaps == 9 && c.cin_pad % 32 == 0 &&
+        // small-batch mode: 3x3 and 7x7 convs that run as launches of their own (the fused units
+        // are planned as without the mode)
+        q.small = small_batch_ && (c.ntaps == 9 || c.ntaps == 49) && c.cin_pad % 32 == 0 &&
                   !(D.fused1 && ((int)ci == fuse1_.a || (int)ci == fuse1_.b));
         // a pool fed by this conv alone runs in its epilogue where the plan, asked for it, has the
         // pooled kernel (POOL_FUSE=0, opk_dev_set, A/B tests: the pools as their own kernels)

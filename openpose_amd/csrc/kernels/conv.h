@@ -145,7 +145,7 @@ struct Conv3Plan {
 };
 // Every decision switch is read here (opk_dev_set; per call, so tests compare variants in one
 // process): CONV3_SMALL, CONV3_W16, CONV3_PERSIST, CONV1_TILE, CONV1_N64W16, CONV3W8_64, SPLIT_W8,
-// CONV3W8N, CONV3W (0 / not), CONV3W8, CONV3S_MAX.  Throws for sizes no kernel covers.
+// CONV3W8N, CONV3W (0 / not), CONV3W8, CONV3S_MAX, CONV7S_BIG.  Throws for sizes no kernel covers.
 // only: a probe tool's choice among the persistent kernels of a conv that supports it (-1: the
 // product rule); plan.family differs from it when the conv does not.
 Conv3Plan conv3_plan(const Conv3Query& q, int only = -1);
@@ -155,8 +155,15 @@ Conv3Plan conv3_plan(const Conv3Query& q, int only = -1);
 int conv3_run_frames(const Conv3Query& q);
 // the small-batch rule: conv3s when the product geometry gives fewer than cus workgroups and
 // conv3s supports the conv and gives more, but no more than kConv3sMaxPerCu per CU (measured: the
-// 64 x 32 tile is level with the 256-position tiles at 2.8 workgroups per CU and 1.8x slower at 5.7)
+// 64 x 32 tile is level with the 256-position tiles at 2.8 workgroups per CU and 1.8x slower at 5.7;
+// the 7x7 tiles keep the cap: at 1 - 8 face / hand crops and 1 - 2 COCO frames every forward
+// measured faster with it)
 constexpr int kConv3sMaxPerCu = 4;
+// the larger (128 x 64) 7x7 tile is taken where it gives a workgroup per this many CUs (3x3: two).
+// Measured: with two, one COCO frame and two face / hand crops take the 64 x 32 tile, whose
+// launched grid (border rows and strip overlap included: 308 / 340 workgroups) no longer fits one
+// round on 256 CUs -- 3.62 against 3.17 ms and 2.26 against 2.01 ms per forward
+constexpr int kConv7sBigPerCus = 4;
 // a.sw / a.nstrips checked against the plan; border, rcp and pbn set from it
 ConvArgs conv3_planned_args(const ConvArgs& a, const Conv3Plan& p);
 
@@ -172,8 +179,9 @@ void launch_conv3(const ConvArgs& a, hipStream_t stream);
 void launch_conv3w(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
 // conv3w8.hip: the same tile with 8 waves of 64 x BN (fewer LDS fragment reads per MFMA)
 void launch_conv3w8(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
-// conv3s.hip: 3x3 / border 1 convs on small tiles (64 x 32 or 128 x 64, 4 waves), bit-identical to
-// the kernels above, for forwards too small to fill the chip with the tiles above
+// conv3s.hip: 3x3 (any border) and 7x7 (border >= 3) convs on small tiles (64 x 32 or 128 x 64,
+// 4 waves), bit-identical to the kernels above, for forwards too small to fill the chip with the
+// tiles above
 void launch_conv3s(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
 
 // conv_head.hip: Mconv6 (1x1, n1 = 256 / 512 outputs, act6) -> Mconv7 (1x1, n2 <= 64 outputs) in

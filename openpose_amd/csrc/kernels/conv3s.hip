@@ -1,4 +1,5 @@
-// conv3s.hip -- small-tile 3x3 convolutions for forwards of a few frames (NetHip small-batch mode).
+// conv3s.hip -- small-tile 3x3 and 7x7 convolutions for forwards of a few frames (NetHip
+// small-batch mode).
 //
 // conv3_kernel's tiles cover 256 or 512 positions by 64 / 96 / 128 outputs: one BODY_25 frame at
 // 656 x 368 gives the 46 x 82 stage layers 16 workgroups on a 256-CU chip.  conv3s_kernel is
@@ -9,14 +10,20 @@
 //       128-channel layer is 4 barriers long, its first two units' loads in flight at once),
 //   128 positions x 64 outputs, 3-tap K units (conv3_kernel's schedule; 76 KB of LDS: two
 //       workgroups per CU),
-// chosen by conv3_plan (conv_plan.cpp).  (A third tile, 128 x 128 with single-tap units and two
-// workgroups per CU, measured slower than conv3_kernel's tiles wherever the rule picked it;
-// DESIGN.md.)  The weights are read from conv3's packing
+// and, for the 7x7 layers of the COCO / MPI / face / hand stages (one crop of 46 x 46 gives
+// conv3_kernel<256,...,7> 10 workgroups), the same two tiles with one tap row (7 taps) per K unit:
+//   64 x 32 under a 384-row halo (90 KB of LDS), 128 x 64 under a 448-row halo (140 KB),
+// chosen by conv3_plan (conv_plan.cpp).  The geometry is in padded positions of any border B
+// (VW = sw + 2 B), so the 3x3 tiles also run the 3x3 layers of a 3-pixel-border net.  (A third
+// tile, 128 x 128 with single-tap units and two workgroups per CU, measured slower than
+// conv3_kernel's tiles wherever the rule picked it; DESIGN.md.)  The weights are read from conv3's
+// packing
 // [cout_pad/PBN][cin_pad/32][ky][kx][PBN][32]: a tile's n-block is the row range
 // [n0 % PBN, n0 % PBN + BN) of every [PBN][32] tap block (BN divides PBN).
 //
-// Arithmetic: the same MFMA, lane assignment and K order (chunk-major, then tap; split precision:
-// x_hi w_lo, x_hi w_hi, x_lo w_hi per chunk) as conv3_kernel, so the outputs are bit-identical.
+// Arithmetic: the same MFMA, lane assignment and K order (chunk-major, then tap ky*KS + kx; split
+// precision: x_hi w_lo, x_hi w_hi, x_lo w_hi per chunk, each over all taps) as conv3_kernel, so the
+// outputs are bit-identical.
 #include "conv.h"
 
 #include <algorithm>
@@ -32,15 +39,16 @@ using namespace conv3dev;
 
 constexpr int kS_NW = 4;   // waves per workgroup
 
-template <int BM, int BN, int HR, int TAPU, bool SPLIT>
+// KS: 3 (TAPU 3 or 9) or 7 (TAPU 7: a tap row per unit -- a chunk's 49 taps x 32 outputs are 100 KB)
+template <int BM, int BN, int HR, int TAPU, bool SPLIT, int KS = 3>
 __global__ __launch_bounds__(64 * kS_NW) void conv3s_kernel(const ConvArgs a)
 {
     constexpr int NW = kS_NW, WAVES_N = 2, WAVES_M = NW / WAVES_N;
     constexpr int WROWS = BM / WAVES_M, WN = BN / WAVES_N;   // wave tile WROWS x WN
     static_assert(WROWS % 16 == 0 && WN % 16 == 0, "wave tiles");
-    static_assert(TAPU == 3 || TAPU == 9, "taps per unit");
+    static_assert((KS == 3 && (TAPU == 3 || TAPU == 9)) || (KS == 7 && TAPU == 7), "taps per unit");
     constexpr int MF = WROWS / 16, NF = WN / 16;
-    constexpr int KT = 9, UPC = KT / TAPU;        // taps, units per 32-channel chunk
+    constexpr int KT = KS * KS, UPC = KT / TAPU;  // taps, units per 32-channel chunk
     constexpr int API = HR / 16;                  // halo DMA instructions per block (16 rows each)
     constexpr int AIW = (API + NW - 1) / NW;      // ... per wave, at most
     constexpr int BROWS = TAPU * BN;              // B rows per unit: tap-major, then channel n
@@ -77,14 +85,14 @@ __global__ __launch_bounds__(64 * kS_NW) void conv3s_kernel(const ConvArgs a)
     const int cptk = SPLIT ? 3 * cpt : cpt;
     const int U = UPC * cptk;
     const ptrdiff_t dlo = SPLIT ? a.in_lo - a.in : 0;
-    // halo row hr = (i*NW + wave)*16 + lrow holds virtual position p0 - VW - 1 + hr
+    // halo row hr = (i*NW + wave)*16 + lrow holds virtual position p0 - (KS/2)*(VW + 1) + hr
     const uint16_t* arow[AIW];
 #pragma unroll
     for (int i = 0; i < AIW; ++i) {
         const int hr = (i * NW + wave) * 16 + lrow;
         const int lp = phys ^ (((hr >> 2) & 1) << 1);
         int f, yy, xx, s;
-        const long pos = g.template map<false>(p0 - (g.VW + 1) + hr, f, yy, xx, s);
+        const long pos = g.template map<false>(p0 - (KS / 2) * (g.VW + 1) + hr, f, yy, xx, s);
         arow[i] = a.in + a.in_coff + pos * a.in_cs + lp * 8;
     }
     // weight row rb = (j*NW + wave)*16 + lrow of a unit: tap rb / BN of the unit, channel rb % BN
@@ -159,8 +167,8 @@ __global__ __launch_bounds__(64 * kS_NW) void conv3s_kernel(const ConvArgs a)
         const uint4* Bs = lds + NAS * ASLOT + (u % 3) * BSLOT;
 #pragma unroll
         for (int k = 0; k < TAPU; ++k) {
-            const int tap = t * TAPU + k;         // ky*3 + kx
-            const int ky = tap / 3, kx = tap - 3 * (tap / 3);
+            const int tap = t * TAPU + k;         // ky*KS + kx
+            const int ky = tap / KS, kx = tap - KS * (tap / KS);
             half8_t fa[MF], fb[NF];
             const int hoff = ky * g.VW + kx;
 #pragma unroll
@@ -270,12 +278,16 @@ __global__ __launch_bounds__(64 * kS_NW) void conv3s_kernel(const ConvArgs a)
 
 }  // namespace
 
-// Reads: a halo row maps to a padded-image position of [0, frames * (H + 2) * (W + 2)), or --
-// outside the virtual image -- to position -1 (Strips::map): within the zeroed guards.  The last
-// strip's columns past the image (nstrips * sw >= W) are masked by Strips::interior.
+// Reads: every halo row goes through Strips::map<false>: it maps to a padded-image position of
+// [0, frames * (H + 2 B) * (W + 2 B)) (B the net's border, 1 or 3), or -- outside the virtual image
+// [0, total) -- to position -1: within the zeroed guards, for either kernel size.  The fragment
+// reads stay inside the halo slot: BM + (KS - 1) * (VW + 1) <= HR (conv3_plan checks it).  The
+// last strip's columns past the image (nstrips * sw >= W) are masked by Strips::interior.
 void launch_conv3s(const ConvArgs& args, const Conv3Plan& p, hipStream_t stream)
 {
     OPK_CHECK_ARG(p.family == Conv3Family::conv3s && !args.pool, "conv3s: unsupported conv");
+    OPK_CHECK_ARG(p.ks * p.ks == args.ntaps && p.bm + (p.ks - 1) * (p.VW + 1) <= p.hr,
+                  "conv3s: strip too wide for the halo");
     OPK_CHECK_ARG(args.in_cs % 8 == 0 && args.in_coff % 8 == 0 && args.in_coff + args.cin_pad <= args.in_cs,
                   "conv3s: input slice unaligned or beyond the buffer");
     bool lo_ok = !args.split || args.in_lo;
@@ -284,16 +296,17 @@ void launch_conv3s(const ConvArgs& args, const Conv3Plan& p, hipStream_t stream)
     const ConvArgs a = conv3_planned_args(args, p);
     const dim3 grid((unsigned)p.grid), block(64 * kS_NW);
     bool launched = false;
-#define OPK3S_TRY(BM_, BN_, HR_, TAPU_)                                                        \
-    if (!launched && p.bm == BM_ && p.bn == BN_ && p.hr == HR_ && p.tapu == TAPU_) {           \
+#define OPK3S_TRY(BM_, BN_, HR_, TAPU_, KS_)                                                   \
+    if (!launched && p.bm == BM_ && p.bn == BN_ && p.hr == HR_ && p.tapu == TAPU_ && p.ks == KS_) { \
         note_launch("%s", p.name);                                                             \
         if (a.split)                                                                           \
-            hipLaunchKernelGGL((conv3s_kernel<BM_, BN_, HR_, TAPU_, true>), grid, block, 0, stream, a); \
+            hipLaunchKernelGGL((conv3s_kernel<BM_, BN_, HR_, TAPU_, true, KS_>), grid, block, 0, stream, a); \
         else                                                                                   \
-            hipLaunchKernelGGL((conv3s_kernel<BM_, BN_, HR_, TAPU_, false>), grid, block, 0, stream, a); \
+            hipLaunchKernelGGL((conv3s_kernel<BM_, BN_, HR_, TAPU_, false, KS_>), grid, block, 0, stream, a); \
         launched = true;                                                                       \
     }
-    OPK3S_TRY(64, 32, 256, 9) OPK3S_TRY(128, 64, 320, 3)
+    OPK3S_TRY(64, 32, 256, 9, 3) OPK3S_TRY(128, 64, 320, 3, 3)
+    OPK3S_TRY(64, 32, 384, 7, 7) OPK3S_TRY(128, 64, 448, 7, 7)
 #undef OPK3S_TRY
     OPK_CHECK_ARG(launched, std::string("no instantiation of ") + p.name);
     OPK_LAUNCH_CHECK();

@@ -205,30 +205,45 @@ Conv3Plan product_plan(const Conv3Query& q, int only)
     return p;
 }
 
-// conv3s tiles {bm, bn, hr, tapu}: the larger where it gives at least a workgroup per two CUs (it
-// stages fewer halo and weight bytes and reads fewer LDS fragments per MFMA), else the smaller
+// conv3s tiles {bm, bn, hr, tapu}: the larger where it gives at least a workgroup per two CUs
+// (7x7: per four, kConv7sBigPerCus) (it stages fewer halo and weight bytes and reads fewer LDS
+// fragments per MFMA), else the smaller
 constexpr int kS_TILES[2][4] = {{64, 32, 256, 9}, {128, 64, 320, 3}};
+// the same two tiles for 7x7 convs, a tap row per K unit: halos of 64 + 6 * 53 and 128 + 6 * 53
+// rows -- a 46-wide crop with its 3 + 3 border columns is one strip
+constexpr int kS_TILES7[2][4] = {{64, 32, 384, 7}, {128, 64, 448, 7}};
 
 bool small_plan(const Conv3Query& q, Conv3Plan& out)
 {
-    if (q.border != 1 || q.ntaps != 9) return false;
+    const bool k7 = q.ntaps == 49;
+    if (!(k7 ? q.border >= 3 : q.ntaps == 9 && q.border >= 1)) return false;
     bool have = false;
     for (int k = 1; k >= 0; --k) {
+        const int* tile = k7 ? kS_TILES7[k] : kS_TILES[k];
         Conv3Plan s{};
         s.family = Conv3Family::conv3s;
-        s.bm = kS_TILES[k][0]; s.bn = kS_TILES[k][1]; s.hr = kS_TILES[k][2]; s.tapu = kS_TILES[k][3];
-        s.minb = 1; s.ks = 3; s.nw = 4;
+        s.bm = tile[0]; s.bn = tile[1]; s.hr = tile[2]; s.tapu = tile[3];
+        s.minb = 1; s.ks = k7 ? 7 : 3; s.nw = 4;
         s.split = q.split;
         s.pbn = n_block(q.cout);
         if (s.pbn % s.bn != 0) continue;
-        strips(s, q.W, 1);
+        // (a border too wide for the halo: no small tile)
+        if ((s.hr - s.bm - (s.ks - 1)) / (s.ks - 1) - 2 * q.border < 8) continue;
+        strips(s, q.W, q.border);
         measure(s, q, s.hr);
-        if (!s.fits) continue;
-        std::snprintf(s.name, sizeof s.name, "conv3s_kernel<%d,%d,%d,%d%s>", s.bm, s.bn, s.hr, s.tapu,
-                      q.split ? ",split" : "");
+        if (!s.fits || s.bm + (s.ks - 1) * (s.VW + 1) > s.hr) continue;
+        // (the 3x3 names as they were: existing launch logs pin them; 7x7: the kernel size last)
+        if (k7)
+            std::snprintf(s.name, sizeof s.name, "conv3s_kernel<%d,%d,%d,%d,%d%s>", s.bm, s.bn, s.hr,
+                          s.tapu, s.ks, q.split ? ",split" : "");
+        else
+            std::snprintf(s.name, sizeof s.name, "conv3s_kernel<%d,%d,%d,%d%s>", s.bm, s.bn, s.hr,
+                          s.tapu, q.split ? ",split" : "");
         out = s;
         have = true;
-        if (k == 1 && 2 * s.workgroups < std::max(q.cus, 1)) continue;   // (kept if the smaller tile is unsupported)
+        // CONV7S_BIG (opk_dev_set, tuning): the larger 7x7 tile from a workgroup per this many CUs
+        const int per = k7 ? std::max(1, dev_switch("CONV7S_BIG", kConv7sBigPerCus)) : 2;
+        if (k == 1 && per * s.workgroups < std::max(q.cus, 1)) continue;   // (kept if the smaller tile is unsupported)
         break;
     }
     return have;

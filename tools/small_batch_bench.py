@@ -1,11 +1,12 @@
-"""Forward time of BODY_25 at the batch sizes an OpenPose worker runs (1 - 8 frames), with the
+"""Forward time of a net (BODY_25 by default) at the batch sizes an OpenPose worker runs (1 - 8 frames), with the
 small-batch mode (Net.set_small_batch) off and on, in fp16 and split precision: HIP events around
 each forward (opk_net_set_timing), milliseconds per forward.
 
     python tools/small_batch_bench.py --out result.json [--flag-off-only] [--repeats 3]
                                       [--warmup 20] [--steps 200]
+                                      [--model builtin:FACE] [--shapes 1x368x368,2x368x368]
 
-Shapes: N in {1, 2, 4, 8} at 368 x 656, and 1 x 368 x 368.  Every repeat runs all variants of all
+Shapes (default): N in {1, 2, 4, 8} at 368 x 656, and 1 x 368 x 368.  Every repeat runs all variants of all
 shapes in turn (variants alternated), so drift hits them alike; the JSON holds every repeat of every
 leg, their mean and their spread (max - min).  The library is the one openpose_amd loads
 (OPK_LIB_PATH selects another build; --flag-off-only for one without the mode).  Needs a GPU: there
@@ -30,8 +31,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--model", default="builtin:BODY_25", help="a builtin net or a prototxt path")
+    ap.add_argument("--shapes", default=None, help="comma-separated NxHxW (default: the BODY_25 set)")
     a = ap.parse_args()
     assert a.warmup >= 20 and a.steps >= 200 and a.repeats >= 1, "at least 20 warm-up and 200 timed forwards"
+    shapes = SHAPES if a.shapes is None else [tuple(int(v) for v in s.split("x")) for s in a.shapes.split(",")]
+    assert all(len(s) == 3 and min(s) > 0 for s in shapes), "--shapes: NxHxW[,NxHxW...]"
 
     import torch
     if not torch.cuda.is_available():
@@ -47,7 +52,7 @@ def main():
     nets = {}
     params = None
     for prec_name, prec, small in variants:
-        net = Net(ctx, "builtin:BODY_25")
+        net = Net(ctx, a.model)
         if params is None:
             params = synth.he_weights(net.convs(), seed=0, out_scale=1.0)
         net.set_params(params)
@@ -59,7 +64,7 @@ def main():
 
     rng = np.random.default_rng(1)
     legs = {}
-    for n, h, w in SHAPES:
+    for n, h, w in shapes:
         x = torch.from_numpy(rng.uniform(-0.5, 0.5, (n, 3, h, w)).astype(np.float32)).cuda()
         for _ in range(a.repeats):
             for key, net in nets.items():
@@ -75,7 +80,7 @@ def main():
                 name = "%dx%dx%d %s %s" % (n, h, w, key[0], "on" if key[1] else "off")
                 legs.setdefault(name, []).append(ms / k)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = {"library": os.path.relpath(os.path.realpath(_lib.LIB_PATH), root), "device": torch.cuda.get_device_name(0),
+    res = {"model": a.model, "library": os.path.relpath(os.path.realpath(_lib.LIB_PATH), root), "device": torch.cuda.get_device_name(0),
            "warmup": a.warmup, "steps": a.steps, "repeats": a.repeats, "legs": {}}
     for name, v in legs.items():
         res["legs"][name] = {"ms": [round(t, 4) for t in v], "mean_ms": round(float(np.mean(v)), 4),
