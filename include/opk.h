@@ -251,7 +251,9 @@ int opk_dev_set(const char* key, int value, int reset);
  *      generated in the library: "builtin:BODY_25", "builtin:COCO_18", "builtin:MPI_15",
  *      "builtin:MPI_15_4", "builtin:HAND", "builtin:FACE" (models/.../pose_deploy*.prototxt).
  *      Supported layers: Convolution 3x3/pad 1, 7x7/pad 3, 1x1; ReLU/PReLU in place after a conv;
- *      MaxPool 2x2/2; channel Concat; the output blob is a Concat or a conv's top. */
+ *      MaxPool 2x2/2; channel Concat; the output blob is a Concat or a conv's top.  Any output
+ *      count, except for the conv that reads the image: at most 64 outputs, a multiple of 4
+ *      (refused at creation otherwise, with the layer's name in opk_last_error). */
 typedef struct opk_net opk_net;
 /* caffemodel (or NULL): trained weights, loaded as caffe::Net::CopyTrainedLayersFrom does
  * (netCaffe.cpp:163-185): every conv whose name is in the file gets its weights, bias and the

@@ -71,6 +71,11 @@ void NetHip::plan(const std::vector<LayerDesc>& layers)
             c.from_image = L.bottom[0] == "image";
             OPK_CHECK_ARG(!c.from_image || (L.kernel_size == 3 && it->second.ch == 3),
                           L.name + ": the input conv must be 3x3 over 3 channels");
+            // conv_image_kernel holds the weights of four 16-channel groups in registers and
+            // stores whole 4-channel groups (launch_conv_image)
+            OPK_CHECK_ARG(!c.from_image || (L.num_output <= 64 && L.num_output % 4 == 0),
+                          L.name + ": the input conv writes at most 64 outputs, a multiple of 4 (" +
+                              std::to_string(L.num_output) + " asked)");
             // in-place activation directly after the conv
             if (li + 1 < layers.size()) {
                 const LayerDesc& A = layers[li + 1];
@@ -162,12 +167,20 @@ void NetHip::plan(const std::vector<LayerDesc>& layers)
             if (p.coff % 8 == 0 && p.coff + need <= bufs_[p.buf].cs) have = true;
         if (pooled || (read && !have) || (B.places.empty() && convs_[B.conv].out32_coff < 0)) {
             const int buf = (int)bufs_.size();
-            bufs_.push_back(BufSpec{B.level, pooled ? round_up(B.ch, 8) : need});
+            // (a pooled conv's buffer too: the pool writes its output with the same channel
+            // stride, and the conv reading that needs whole 32-channel chunks, the padding zero)
+            bufs_.push_back(BufSpec{B.level, need});
             B.places.insert(B.places.begin(), Placement{buf, 0});
         }
         ConvPlan& c = convs_[B.conv];
         c.outs = B.places;
         OPK_CHECK_ARG(c.outs.size() <= (size_t)kConvMaxDst, c.info.name + ": too many consumers");
+        if (c.from_image) {   // what launch_conv_image takes: 8-byte aligned fp16 slices only
+            OPK_CHECK_ARG(c.out32_coff < 0, c.info.name + ": the input conv cannot write the output blob");
+            for (const auto& p : c.outs)
+                OPK_CHECK_ARG(p.coff % 4 == 0, c.info.name + ": the input conv needs concat offsets "
+                                                             "that are multiples of 4");
+        }
     }
     // pass 4: pool output buffers, then conv inputs and GEMM geometry
     int pi = 0;
@@ -175,10 +188,12 @@ void NetHip::plan(const std::vector<LayerDesc>& layers)
         if (L.type != "Pooling") continue;
         PoolPlan& p = pools_[pi++];
         p.in_buf = blobs[L.bottom[0]].places.at(0).buf;
-        OPK_CHECK_ARG(bufs_[p.in_buf].cs == round_up(p.channels, 8),
+        // one channel stride for both sides (launch_maxpool2's C): 32-channel chunks, as the
+        // convs reading the pooled image need; the padding channels stay zero on both sides
+        OPK_CHECK_ARG(bufs_[p.in_buf].cs == round_up(p.channels, 32),
                       L.name + ": pool input must own its buffer");
         const int buf = (int)bufs_.size();
-        bufs_.push_back(BufSpec{p.level_in + 1, round_up(p.channels, 8)});
+        bufs_.push_back(BufSpec{p.level_in + 1, round_up(p.channels, 32)});
         blobs[L.top[0]].places.push_back(Placement{buf, 0});
         p.out_buf = buf;
     }

@@ -13,6 +13,9 @@ that launch, element by element (never sampled):
     store cannot hide (tests/test_launch_check.py injects each of them);
   * heads whose only consumer is the net_output concat: their fp32 slice of net_output too (the
     concat offset);
+  * every other destination of a conv (its slice of each concat it is a member of; blob() reads
+    placement 0 only): the concat's slice equals the member's own blob bit for bit
+    (check_concat_slices) -- the consumer of a concat is referenced to whatever the concat holds;
   * stand-alone pools (Pooling layers no conv unit of the log took into its epilogue): the output
     blob equals the max pool of the input blob exactly -- a max of fp16 values is exact, and in
     split precision the pooled hi + lo is the largest hi + lo of the window, exact in fp32.
@@ -129,8 +132,10 @@ def check_launches(net, graph, params, x, frames, split=False, log=None):
             off += chans[b]
         assert off == net.blob("net_output", (frames[0], 1)).shape[1], off
 
+    check_concat_slices(net, graph, frames)
+
     # stand-alone pools: exact
-    fused = {u["pool"]["name"] for u in units.values() if u["pool"] is not None}
+    fused ={u["pool"]["name"] for u in units.values() if u["pool"] is not None}
     alone = [l for l in graph if l["type"] == "Pooling" and l["name"] not in fused]
     assert len(alone) == len(pool_kernels), ("pool launches", [l["name"] for l in alone], pool_kernels)
     for l, kernel in zip(alone, pool_kernels):
@@ -150,6 +155,41 @@ def check_launches(net, graph, params, x, frames, split=False, log=None):
             amax = max(amax, float(np.abs(ref).max()))
         rows.append(Row(l["name"], kernel, 0.0, 0.0, amax))
     return rows
+
+
+def check_concat_slices(net, graph, frames):
+    """Every destination of a conv, not only its first: for every Concat but net_output and every
+    member, the slice [off, off + ch) of the concat's blob holds the bits of the member's own blob
+    (split precision: hi + lo of the same stored pair is the same float).  Trivially true where
+    the member's only placement is that slice; a check of the second to sixth store of a conv that
+    also has a buffer of its own or is a member of several concats.  Returns the number of
+    (concat, member) pairs compared."""
+    chans = {l["top"][0]: l["num_output"] for l in graph if l["type"] == "Convolution"}
+    pairs = 0
+    for l in graph:
+        if l["type"] != "Concat" or l["top"][0] == "net_output":
+            continue
+        cat = l["top"][0]
+        for f in frames:
+            whole = np.ascontiguousarray(net.blob(cat, (f, 1)), np.float32)
+            off = 0
+            for b in l["bottom"]:
+                own = np.ascontiguousarray(net.blob(b, (f, 1)), np.float32)
+                assert own.shape[1] == chans[b], (b, own.shape, chans[b])
+                part = np.ascontiguousarray(whole[:, off:off + chans[b]])
+                assert part.shape == own.shape, (cat, b, part.shape, own.shape)
+                bad = part.view(np.uint32) != own.view(np.uint32)
+                if bad.any():
+                    i = tuple(int(v) for v in np.unravel_index(np.argmax(bad), bad.shape))
+                    raise AssertionError("%s (concat) member %s frame %d: %d of %d elements of the slice "
+                                         "[%d, %d) differ from the member's own blob; first at %s: "
+                                         "concat %r member %r tol 0"
+                                         % (cat, b, f, int(bad.sum()), bad.size, off, off + chans[b], i,
+                                            float(part[i]), float(own[i])))
+                off += chans[b]
+                pairs += f == frames[0]
+            assert off == whole.shape[1], (cat, off, whole.shape)
+    return pairs
 
 
 def print_rows(rows, title=""):

@@ -4,9 +4,11 @@ test_gpu_launch_matrix.py) would fail on a wrong lane, tap, bias, slope, pooling
 store or missing split pass.
 
 The checker is driven with a stand-in net (EmulatedNet) whose blob() and launch_log() are served
-from an emulation of a 4-layer graph at 2 x 24 x 40 (conv 3 -> 64, conv 64 -> 64 + 2x2 pool,
-conv 64 -> 96 PReLU, 1x1 head to the fp32 net_output), in both precisions and with the pool in the
-conv's epilogue ("c2+pool") or as its own launch.  The emulation evaluates every conv in float64
+from an emulation of a small graph at 2 x 24 x 40 (conv 3 -> 64, conv 64 -> 64 + 2x2 pool,
+conv 64 -> 96 PReLU, a 1x1 conv 96 -> 20, the inner concat of the two -- the 96-channel member at
+offset 20, no multiple of 8, and with a reader of its own -- and a 1x1 head from the concat to the
+fp32 net_output), in both precisions and with the pool in the conv's epilogue ("c2+pool") or as
+its own launch.  The emulation evaluates every conv in float64
 (torch) and rounds at the stores, so the clean stand-in differs from the checker's references
 (oracle/fp16.py on the C oracle's fp32 sums; oracle/split.py) by what a correct kernel may differ
 by -- the summation order and the stored pair's residue -- and must pass; each injected defect
@@ -18,7 +20,8 @@ import pytest
 from oracle import fp16 as emu
 from oracle import split as sp
 from tests import prototxt
-from tests.launch_check import C_ACC, C_ACC_CHAINED, C_SPLIT, check_launches, random_params
+from tests.launch_check import (C_ACC, C_ACC_CHAINED, C_SPLIT, check_concat_slices, check_launches,
+                                random_params)
 
 N, H, W = 2, 24, 40
 DEFECTS = ["tap", "shift_x", "bias", "slope", "pool_partner", "stale_group"]
@@ -34,7 +37,9 @@ def graph4():
         return out
     L = conv("c1", "image", 64, 3, "relu") + conv("c2", "c1", 64, 3, "relu")
     L.append(dict(name="p1", type="Pooling", bottom=["c2"], top=["p1"], kernel_size=2, stride=2))
-    L += conv("c3", "p1", 96, 3, "prelu") + conv("c4", "c3", 26, 1)
+    L += conv("c3", "p1", 96, 3, "prelu") + conv("c5", "c3", 20, 1)
+    L.append(dict(name="cat", type="Concat", bottom=["c5", "c3"], top=["cat"]))
+    L += conv("c4", "cat", 26, 1)
     L.append(dict(name="net_output", type="Concat", bottom=["c4"], top=["net_output"]))
     return prototxt.parse(prototxt.emit(L))
 
@@ -101,7 +106,12 @@ class EmulatedNet:
                 if not fuse_pool:
                     self.log.append(("pool", "emulated_pool"))
             elif l["type"] == "Concat":
-                self.blobs[l["top"][0]] = np.concatenate([cur[b] for b in l["bottom"]], axis=1)
+                v = np.concatenate([cur[b] for b in l["bottom"]], axis=1)
+                if defect == "stale_concat_slice" and l["top"][0] == "cat":
+                    # one 4-channel group of c3's slice (offset 20) of the last frame not written;
+                    # c3's own buffer, which c5 reads, is right
+                    v[N - 1, 20 + 8:20 + 12] = v[0, 20 + 8:20 + 12]
+                cur[l["top"][0]] = self.blobs[l["top"][0]] = v
 
     def launch_log(self):
         return list(self.log)
@@ -140,7 +150,8 @@ def test_clean_emulation_is_accepted(case, split, fuse_pool):
     layer logged by three frame runs is checked once), the stand-alone pool as a row of its own."""
     rows = _run(case, split, fuse_pool, runs=3)
     layers = [r.layer for r in rows]
-    assert layers == (["c1", "c2+pool", "c3", "c4"] if fuse_pool else ["c1", "c2", "c3", "c4", "p1"])
+    assert layers == (["c1", "c2+pool", "c3", "c5", "c4"] if fuse_pool
+                      else ["c1", "c2", "c3", "c5", "c4", "p1"])
     assert all(0 <= r.frac < 1 for r in rows)
     assert rows[2].kernel == "emulated<c3>"
     # the stand-in's float64 sums differ from the fp16 reference's fp32 sums: the check is not
@@ -178,6 +189,29 @@ def test_split_without_the_lo_pass_is_rejected(case, fuse_pool):
     with pytest.raises(AssertionError) as e:
         _run(case, True, fuse_pool, "no_xlo_pass")
     assert str(e.value).startswith("c3 (emulated<c3>)"), str(e.value)
+
+
+@pytest.mark.parametrize("fuse_pool", [True, False])
+@pytest.mark.parametrize("split", [False, True])
+def test_stale_concat_slice_is_rejected(case, split, fuse_pool):
+    """A conv's second destination: one 4-channel group of one frame of c3's slice of the concat
+    differs from c3's own buffer.  Every per-launch reference passes -- c5 reads the right buffer,
+    and the head's reference is fed the concat as it is -- so only the slice check can raise; it
+    names the concat, the member, the frame, the element and both values."""
+    graph, params, x = case
+    net = EmulatedNet(graph, params, x, split, fuse_pool, "stale_concat_slice")
+    assert check_concat_slices(EmulatedNet(graph, params, x, split, fuse_pool), graph, [0, N - 1]) == 2
+    with pytest.raises(AssertionError) as e:
+        check_launches(net, graph, params, x, [0, N - 1], split=split)
+    msg = str(e.value)
+    assert msg.startswith("cat (concat) member c3 frame %d: " % (N - 1)), msg
+    assert "[20, 116)" in msg and "first at (0, 8, " in msg, msg
+    for word in ("concat", "member", "tol 0"):
+        assert word in msg, msg
+    # the defect is in the concat alone, and in the last frame alone
+    assert check_concat_slices(net, graph, [0]) == 2
+    with pytest.raises(AssertionError):
+        check_concat_slices(net, graph, [N - 1])
 
 
 def test_wrong_net_output_offset_is_rejected(case):
