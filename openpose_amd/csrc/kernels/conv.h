@@ -179,9 +179,9 @@ void launch_conv3(const ConvArgs& a, hipStream_t stream);
 void launch_conv3w(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
 // conv3w8.hip: the same tile with 8 waves of 64 x BN (fewer LDS fragment reads per MFMA)
 void launch_conv3w8(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
-// conv3s.hip: 3x3 (any border) and 7x7 (border >= 3) convs on small tiles (64 x 32 or 128 x 64,
-// 4 waves), bit-identical to the kernels above, for forwards too small to fill the chip with the
-// tiles above
+// conv3.hip: 3x3 (any border) and 7x7 (border >= 3) convs on small tiles (64 x 32 or 128 x 64,
+// conv3_kernel with 4 waves; logged as conv3s_kernel<...>), bit-identical to the kernels above,
+// for forwards too small to fill the chip with the tiles above
 void launch_conv3s(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
 
 // conv_head.hip: Mconv6 (1x1, n1 = 256 / 512 outputs, act6) -> Mconv7 (1x1, n2 <= 64 outputs) in

@@ -1,9 +1,9 @@
 // conv3.hip -- 3x3 convolutions on gfx950 MFMA with the input halo staged ONCE per channel chunk.
 //
 // Role: Caffe ConvolutionLayer + fused PReLU/ReLU + concat-by-slice (netCaffe.cpp:248) for every
-// 3x3 layer of the net except conv1_1 (which reads the 3-channel image).  The implicit GEMM of
-// conv2.hip re-reads each input row nine times (once per tap) and is bound by the per-CU LDS fill
-// rate (profiles/round1); here each input row is staged once per 32-channel chunk.
+// 3x3 layer of the net except conv1_1 (which reads the 3-channel image).  A plain implicit GEMM
+// re-reads each input row nine times (once per tap) and is bound by the per-CU LDS fill rate
+// (profiles/round1); here each input row is staged once per 32-channel chunk.
 //
 // Row space ("virtual image").  The padded NHWC image [frames][H+2][W+2] is cut into vertical
 // strips of sw interior columns (nstrips = ceil(W / sw); sw = W for narrow images).  Each strip is
@@ -23,6 +23,9 @@
 // windows the taps read (brute-forced over all ds_read_b128 lane groups and window offsets).
 //
 // Tiles: BM x BN = 256 x 128 (8 waves as 4 x 2) or 512 x 64 (8 x 1); every wave owns 64 x 64.
+// Forwards of a few frames (small-batch mode) take 64 x 32 or 128 x 64 tiles of 4 waves
+// (launch_conv3s), one BODY_25 frame at 656 x 368 giving the 46 x 82 stage layers only 16 of the
+// large tiles on a 256-CU chip; same MFMA, lane assignment and K order, so bit-identical outputs.
 // The MFMAs compute C^T (weights are the A operand) so each lane ends with 4 consecutive output
 // channels of one position: the epilogue packs them to 8 fp16 bytes and stores straight from
 // registers (no LDS pass).
@@ -59,24 +62,30 @@ __device__ unsigned long long* opk3_stamps;
 #endif
 
 
-// TAPU: taps per K unit (3 = one ky row of taps, 1 = a single tap); MINB: workgroups per CU the
-// LDS budget allows (2 -> 80 KB: the other workgroup's MFMAs cover this one's prologue, barrier
-// and epilogue stalls).
-// KS: 3 (3x3, pad 1) or 1 (1x1: the "halo" is the tile itself, one tap per chunk).
-// NW: waves per workgroup (8, or 16 for the 512-row tiles of the one-per-CU variant).
+// TAPU: taps per K unit, a divisor of KS*KS (1 = a single tap, KS = one ky row of taps, 9 = a
+// whole 3x3 chunk); MINB: workgroups per CU the LDS budget allows (2 -> 80 KB: the other
+// workgroup's MFMAs cover this one's prologue, barrier and epilogue stalls).
+// KS: 3 (3x3), 7 (7x7) or 1 (1x1: the "halo" is the tile itself, one tap per chunk).
+// NW: waves per workgroup: 8, 16 for the 512-row tiles of the one-per-CU variant, or 4 (as 2 x 2)
+// for the small tiles of the small-batch mode (launch_conv3s below), which also
+//   * read their BN weight rows out of every [a.pbn][32] tap block of conv3's packing
+//     [cout_pad/PBN][cin_pad/32][ky][kx][PBN][32]: rows [n0 % PBN, n0 % PBN + BN), BN divides PBN
+//     (the other tiles' BN is the packing block: a unit's weights are one contiguous run);
+//   * fetch bias and slopes before the K loop;
+//   * have no 16-byte epilogue.
 // SPLIT: split precision (ConvArgs::split, conv.h) -- a separate instantiation, so the fp16 path
 // is unchanged
 template <int BM, int BN, int HR, int TAPU, int MINB, int KS, int NW = 8, bool SPLIT = false>
 __global__ __launch_bounds__(64 * NW, MINB) __attribute__((amdgpu_waves_per_eu(NW / 4 * MINB)))
 void conv3_kernel(const ConvArgs a)
 {
-    constexpr int WAVES_N = BN % 64 == 0 ? BN / 64 : 2, WAVES_M = NW / WAVES_N;
+    constexpr bool SMALL = NW == 4;
+    constexpr int WAVES_N = !SMALL && BN % 64 == 0 ? BN / 64 : 2, WAVES_M = NW / WAVES_N;
     constexpr int WROWS = BM / WAVES_M;            // wave tile WROWS x WN
     constexpr int WN = BN / WAVES_N;
     static_assert(WROWS % 16 == 0 && WROWS <= 128 && WN % 16 == 0 && WN <= 64, "wave tiles");
-    static_assert(TAPU == 1 || TAPU == 3, "taps per unit");
-    static_assert(KS == 3 || (KS == 7 && TAPU == 1) || (KS == 1 && TAPU == 1 && HR == BM),
-                  "3x3, 7x7 (single-tap units) or 1x1 (one tap, halo = tile)");
+    static_assert(KS == 3 || KS == 7 || (KS == 1 && HR == BM), "3x3, 7x7 or 1x1 (one tap, halo = tile)");
+    static_assert((KS * KS) % TAPU == 0, "taps per unit");
     constexpr int MF = WROWS / 16, NF = WN / 16;
     constexpr int KT = KS * KS;                   // taps
     constexpr int UPC = KT / TAPU;                // units per 32-channel chunk
@@ -84,12 +93,14 @@ void conv3_kernel(const ConvArgs a)
     constexpr int AIW = (API + NW - 1) / NW;      // ... per wave, at most
     constexpr int BROWS = TAPU * BN;              // B rows per unit: tap-major, then channel n
     constexpr int BPI = BROWS / 16;               // B DMA instructions per block per unit
+    constexpr int BIW = (BPI + NW - 1) / NW;      // ... per wave, at most
     constexpr int ASLOT = HR * 4;                 // 16-byte pieces per halo slot
     constexpr int NAS = UPC >= 2 ? 2 : 3;         // halo slots: unit u+2 may start chunk c+2 if UPC == 1
     constexpr int BSLOT = BROWS * 4;
     constexpr int LDS_PIECES = NAS * ASLOT + 3 * BSLOT;
     static_assert(HR % 16 == 0 && BROWS % 16 == 0, "DMA granularity");
     static_assert(LDS_PIECES * 16 * MINB <= 160 * 1024, "LDS budget");
+    static_assert(!SMALL || AIW + BIW <= 15, "vm_wait_rt range");
     __shared__ uint4 lds[LDS_PIECES];
 
     OPK3_STAMP(0);
@@ -98,10 +109,7 @@ void conv3_kernel(const ConvArgs a)
     const int wm = wave / WAVES_N, wn = wave - (wave / WAVES_N) * WAVES_N;
     const Strips g(a);
     const int nn = (a.cout + BN - 1) / BN;
-    // XCD-aware bijective tile order (see conv2.hip)
-    const int nblk = gridDim.x;
-    const int xcd = blockIdx.x & 7, qq = nblk >> 3, rr = nblk & 7;
-    const int tix = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (blockIdx.x >> 3);
+    const int tix = tile_order(blockIdx.x, gridDim.x);
     const int p0 = (tix / nn) * BM;
     const int nb = tix - (tix / nn) * nn;
     const int n0 = nb * BN;
@@ -116,8 +124,8 @@ void conv3_kernel(const ConvArgs a)
     const int cptk = SPLIT ? 3 * cpt : cpt;       // K (virtual) chunks
     const int U = UPC * cptk;                     // units (chunk, taps)
     const ptrdiff_t dlo = SPLIT ? a.in_lo - a.in : 0;   // hi -> lo twin (elements)
-    // halo row hr = (i*8 + wave)*16 + lrow holds virtual position p0 - VW - 1 + hr; its image
-    // address (chunk 0, swizzled piece) is fixed for the whole tile
+    // halo row hr = (i*NW + wave)*16 + lrow holds virtual position p0 - (KS/2)*(VW + 1) + hr; its
+    // image address (chunk 0, swizzled piece) is fixed for the whole tile
     const uint16_t* arow[AIW];
 #pragma unroll
     for (int i = 0; i < AIW; ++i) {
@@ -128,28 +136,35 @@ void conv3_kernel(const ConvArgs a)
         const long pos = g.template map<false>(p0 - (KS / 2) * (g.VW + 1) + hr, f, yy, xx, s);
         arow[i] = a.in + a.in_coff + pos * a.in_cs + lp * 8;
     }
-    // this wave issues halo instructions i*8 + wave < API and B instructions j*8 + wave < BPI
+    // this wave issues halo instructions i*NW + wave < API and B instructions j*NW + wave < BPI
     const int ai = (API - wave + NW - 1) / NW;
     const int bi = (BPI - wave + NW - 1) / NW;
-    // split: the packed weights hold w_hi and w_lo (2 cpt chunks per n-block); virtual chunk
-    // 3c + k reads w_lo chunk c (cpt + c) for k = OPK_SPLIT_WLO_K (conv.h), w_hi chunk c
-    // otherwise -- OPK3_WUNIT (the order of conv3w8_kernel, so the two stay bit-identical)
-    const uint16_t* wbase = a.w + (size_t)nb * (SPLIT ? 2 * cpt : cpt) * KT * BN * 32;
-#define OPK3_WUNIT(u_)                                                                        \
-    (!SPLIT ? (u_) : ({                                                                       \
-        const int cc_ = (u_) / UPC;                                                           \
-        const int wc_ = cc_ % 3 == OPK_SPLIT_WLO_K ? cpt + cc_ / 3 : cc_ / 3;                 \
-        wc_ * UPC + ((u_) - cc_ * UPC);                                                       \
-    }))
+    // the packed n-block (PBN channels, split: w_hi and w_lo, 2 cpt chunks) this tile's BN
+    // channels lie in, and their first row in it
+    const int pbn = SMALL ? a.pbn : BN;
+    const int pb = SMALL ? n0 / pbn : nb, r0 = n0 - pb * pbn;
+    const uint16_t* wbase = a.w + (size_t)pb * (SPLIT ? 2 * cpt : cpt) * KT * pbn * 32;
+    // weight row rb = (j*NW + wave)*16 + lrow of a unit: tap rb / BN of the unit, channel rb % BN
+    int boff[SMALL ? BIW : 1];
+    if constexpr (SMALL) {
+#pragma unroll
+        for (int j = 0; j < BIW; ++j) {
+            const int rb = (j * NW + wave) * 16 + lrow;
+            boff[j] = ((rb / BN) * pbn + r0 + rb % BN) * 32 + (phys ^ (((rb >> 2) & 1) << 1)) * 8;
+        }
+    }
     // halo slot of virtual chunk c_ and whether its first unit issues a halo DMA
 #define OPK3_ASLOT(c_) (!SPLIT ? (c_) % NAS : ((c_) % 3 == 2 ? 1 : (UPC == 1 ? 2 * (((c_) / 3) & 1) : 0)))
 #define OPK3_HALO(c_) (!SPLIT || (c_) % 3 != 1)
+    // packed weight chunk of virtual chunk c_ (split: the cpt w_lo chunks follow the cpt w_hi
+    // chunks; the order of conv3w8_kernel, so the two stay bit-identical)
+#define OPK3_WCHUNK(c_) ((c_) % 3 == OPK_SPLIT_WLO_K ? cpt + (c_) / 3 : (c_) / 3)
 
 #define OPK3_ISSUE(u_)                                                                        \
     do {                                                                                      \
-        const int c_ = (u_) / UPC;                                                            \
+        const int c_ = (u_) / UPC, tu_ = (u_) - c_ * UPC;                                     \
         /* dev probe only: 6 = no halo DMA, 7 = no weight DMA after the prologue */           \
-        if ((u_) - c_ * UPC == 0 && OPK3_HALO(c_) && (OPK3_ABLATE != 6 || (u_) < 2)) {       \
+        if (tu_ == 0 && OPK3_HALO(c_) && (OPK3_ABLATE != 6 || (u_) < 2)) {                    \
             const int as_ = OPK3_ASLOT(c_) * ASLOT;                                           \
             /* split: k = 2 reads the lo twin, k = 0 the hi image */                          \
             const ptrdiff_t ao_ = !SPLIT ? (ptrdiff_t)c_ * 32                                  \
@@ -162,13 +177,17 @@ void conv3_kernel(const ConvArgs a)
                         16, 0, 0);                                                            \
         }                                                                                     \
         const int bs_ = NAS * ASLOT + ((u_) % 3) * BSLOT;                                     \
-        const uint16_t* ub_ = wbase + (size_t)OPK3_WUNIT(u_) * BROWS * 32;                    \
-        _Pragma("unroll") for (int j_ = 0; j_ < (BPI + NW - 1) / NW; ++j_) {                  \
+        /* the unit's weights: TAPU tap blocks of pbn rows (SMALL), else one run of BROWS rows */ \
+        const int wc_ = !SPLIT ? c_ : OPK3_WCHUNK(c_);                                        \
+        const uint16_t* ub_ =                                                                 \
+            SMALL ? wbase + ((size_t)wc_ * KT + tu_ * TAPU) * pbn * 32                        \
+                  : wbase + (size_t)(!SPLIT ? (u_) : wc_ * UPC + tu_) * BROWS * 32;           \
+        _Pragma("unroll") for (int j_ = 0; j_ < BIW; ++j_) {                                  \
             if ((BPI % NW == 0 || j_ * NW + wave < BPI) && (OPK3_ABLATE != 7 || (u_) < 2)) {  \
                 const int rb_ = (j_ * NW + wave) * 16 + lrow;                                 \
                 const int lp_ = phys ^ (((rb_ >> 2) & 1) << 1);                               \
                 __builtin_amdgcn_global_load_lds(                                             \
-                    (const void*)(ub_ + rb_ * 32 + lp_ * 8),                                  \
+                    (const void*)(SMALL ? ub_ + boff[j_] : ub_ + rb_ * 32 + lp_ * 8),         \
                     (__attribute__((address_space(3))) void*)(&lds[bs_ + (j_ * NW + wave) * 64]), \
                     16, 0, 0);                                                                \
             }                                                                                 \
@@ -183,7 +202,8 @@ void conv3_kernel(const ConvArgs a)
 
     const int r16 = lane & 15, q = lane >> 4;
     // bias and negative-side multiplier (1: identity, 0: ReLU, slope: PReLU) of this lane's
-    // output channels; fetched before the K loop when registers allow (MINB == 1)
+    // output channels; fetched before the K loop when registers allow (the older loads retire
+    // before the K loop's DMAs: its counted waits cover them)
     float4_t bv[NF], mv[NF];
     const float neg = a.act == 1 ? 0.f : 1.f;
 #define OPK3_BIAS()                                                                           \
@@ -197,7 +217,7 @@ void conv3_kernel(const ConvArgs a)
         }                                                                                     \
     } while (0)
     // registers to spare across the K loop
-    constexpr bool BIAS_EARLY = MINB == 1 && NW == 8 && MF * NF <= 16;
+    constexpr bool BIAS_EARLY = SMALL || (MINB == 1 && NW == 8 && MF * NF <= 16);
     if constexpr (BIAS_EARLY) OPK3_BIAS();
 
     OPK3_ISSUE(0);
@@ -249,7 +269,7 @@ void conv3_kernel(const ConvArgs a)
         }
     }
 #undef OPK3_ISSUE
-#undef OPK3_WUNIT
+#undef OPK3_WCHUNK
 #undef OPK3_ASLOT
 #undef OPK3_HALO
     OPK3_STAMP(2);
@@ -257,8 +277,8 @@ void conv3_kernel(const ConvArgs a)
 #undef OPK3_BIAS
 
     // ---- epilogue straight from registers ------------------------------------------------------
-    // lane (q, r16) of fragment (i, j) holds output channels ch..ch+3 (ch = n0 + wn*64 + j*16 + 4q)
-    // of virtual position p0 + wm*64 + i*16 + r16; border and out-of-image positions are dropped.
+    // lane (q, r16) of fragment (i, j) holds output channels ch..ch+3 (ch = n0 + wn*WN + j*16 + 4q)
+    // of virtual position p0 + wm*WROWS + i*16 + r16; border and out-of-image positions are dropped.
     long prow[MF];
     bool pok[MF];
     int pbase = p0 + wm * WROWS + r16;
@@ -296,7 +316,7 @@ void conv3_kernel(const ConvArgs a)
     // 16-byte stores (see conv3p_kernel): fragment pairs exchanged between lane rows q and q^1 by
     // v_permlane16_swap, each lane then holds 8 consecutive channels of its position.  Needs whole
     // 8-channel groups and 16-byte aligned destination slices; CONV3_WIDE=0 (opk_dev_set) disables.
-    bool wide = NF % 2 == 0 && (a.cout & 7) == 0 && !a.out32 && a.wide;
+    bool wide = !SMALL && NF % 2 == 0 && (a.cout & 7) == 0 && !a.out32 && a.wide;
     for (int d = 0; d < a.ndst; ++d) wide = wide && ((a.dst_coff[d] | a.dst_cs[d]) & 7) == 0;
     if (wide) {
         const int cw = n0 + wn * WN + 16 * (q & 1) + 8 * (q >> 1);
@@ -449,8 +469,7 @@ __global__ __launch_bounds__(64 * kP_NW, 1) void conv3p_kernel(const ConvArgs a)
     const int ntm = (g.total + BM - 1) / BM;
     // XCD-aware bijective order; block -> (n-block, first m-tile); m-tiles stride by G / nn
     const int G = gridDim.x;
-    const int xcd = blockIdx.x & 7, qq = G >> 3, rr = G & 7;
-    const int tix = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (blockIdx.x >> 3);
+    const int tix = tile_order(blockIdx.x, G);
     const int per_n = G / nn;
     const int nb = tix % nn;
     int m = tix / nn;
@@ -726,6 +745,54 @@ __global__ __launch_bounds__(64 * kP_NW, 1) void conv3p_kernel(const ConvArgs a)
 
 
 }  // namespace
+
+// The small tiles of the small-batch mode (NetHip): conv3_kernel with 4 waves (2 x 2) on
+//   64 positions x 32 outputs, one K unit per chunk (all 9 taps' weights staged together: a
+//       128-channel layer is 4 barriers long, its first two units' loads in flight at once),
+//   128 positions x 64 outputs, 3-tap K units (76 KB of LDS: two workgroups per CU),
+// and, for the 7x7 layers of the COCO / MPI / face / hand stages, the same two tiles with one tap
+// row (7 taps) per K unit (a chunk's 49 taps x 32 outputs would be 100 KB): 64 x 32 under a
+// 384-row halo (90 KB of LDS), 128 x 64 under a 448-row halo (140 KB); chosen by conv3_plan
+// (conv_plan.cpp).  The launch log keeps the plan's name for them, conv3s_kernel<BM,BN,HR,TAPU[,KS]>.
+// The geometry is in padded positions of any border B (VW = sw + 2 B), so the 3x3 tiles also run
+// the 3x3 layers of a 3-pixel-border net.  (A third tile, 128 x 128 with single-tap units and two
+// workgroups per CU, measured slower than the large tiles wherever the rule picked it; DESIGN.md.)
+//
+// Reads: every halo row goes through Strips::map<false>: it maps to a padded-image position of
+// [0, frames * (H + 2 B) * (W + 2 B)) (B the net's border, 1 or 3), or -- outside the virtual image
+// [0, total) -- to position -1: within the zeroed guards, for either kernel size.  The fragment
+// reads stay inside the halo slot: BM + (KS - 1) * (VW + 1) <= HR (conv3_plan checks it).  The
+// last strip's columns past the image (nstrips * sw >= W) are masked by Strips::interior.
+void launch_conv3s(const ConvArgs& args, const Conv3Plan& p, hipStream_t stream)
+{
+    OPK_CHECK_ARG(p.family == Conv3Family::conv3s && !args.pool, "conv3s: unsupported conv");
+    OPK_CHECK_ARG(p.ks * p.ks == args.ntaps && p.bm + (p.ks - 1) * (p.VW + 1) <= p.hr,
+                  "conv3s: strip too wide for the halo");
+    OPK_CHECK_ARG(args.in_cs % 8 == 0 && args.in_coff % 8 == 0 && args.in_coff + args.cin_pad <= args.in_cs,
+                  "conv3s: input slice unaligned or beyond the buffer");
+    bool lo_ok = !args.split || args.in_lo;
+    for (int d = 0; d < args.ndst && args.split; ++d) lo_ok = lo_ok && args.dst_lo[d];
+    OPK_CHECK_ARG(lo_ok, "conv3s split: lo twins required");
+    const ConvArgs a = conv3_planned_args(args, p);
+    const dim3 grid((unsigned)p.grid), block(64 * 4);
+    bool launched = false;
+    // MINB = 1 for all four: the 128 x 64 3x3 tile's 76 KB of LDS do fit twice per CU, but MINB = 2
+    // (waves_per_eu 2) moves its accumulators from AGPRs into VGPRs, a schedule nobody measured
+#define OPK3S_TRY(BM_, BN_, HR_, TAPU_, KS_)                                                   \
+    if (!launched && p.bm == BM_ && p.bn == BN_ && p.hr == HR_ && p.tapu == TAPU_ && p.ks == KS_) { \
+        note_launch("%s", p.name);                                                             \
+        if (a.split)                                                                           \
+            hipLaunchKernelGGL((conv3_kernel<BM_, BN_, HR_, TAPU_, 1, KS_, 4, true>), grid, block, 0, stream, a); \
+        else                                                                                   \
+            hipLaunchKernelGGL((conv3_kernel<BM_, BN_, HR_, TAPU_, 1, KS_, 4>), grid, block, 0, stream, a); \
+        launched = true;                                                                       \
+    }
+    OPK3S_TRY(64, 32, 256, 9, 3) OPK3S_TRY(128, 64, 320, 3, 3)
+    OPK3S_TRY(64, 32, 384, 7, 7) OPK3S_TRY(128, 64, 448, 7, 7)
+#undef OPK3S_TRY
+    OPK_CHECK_ARG(launched, std::string("no instantiation of ") + p.name);
+    OPK_LAUNCH_CHECK();
+}
 
 // The public entry: plans the conv (conv_plan.cpp decides kernel, tile, strips and grid) and
 // launches what the plan says.

@@ -1,6 +1,7 @@
 // conv3_dev.h -- device helpers shared by the halo implicit-GEMM conv kernels (conv3.hip,
-// conv3w.hip): vector types, the LDS swizzle of 64-byte rows, counted vmcnt waits, the
-// "virtual image" strip geometry (see conv3.hip's header comment).
+// conv3w.hip, conv3w8.hip, conv_head.hip, conv1_fused.hip): vector types, the LDS swizzle of
+// 64-byte rows, counted vmcnt waits, the XCD-aware tile order, the "virtual image" strip geometry
+// (see conv3.hip's header comment), the epilogue activation and buffer-store resources.
 #pragma once
 #include "conv.h"
 
@@ -55,6 +56,15 @@ __device__ __forceinline__ void vm_wait_rt(int n)
     case 15: vm_wait<15>(); break;
     default: vm_wait<0>(); break;
     }
+}
+
+// XCD-aware bijective tile order: consecutive workgroups go round the 8 XCDs, so workgroup b of a
+// grid of G takes tile (start of XCD b % 8's contiguous range) + b / 8 -- neighbouring tiles (the
+// n-blocks of one m-tile, overlapping halos) share an XCD's L2.  A bijection of [0, G) for any G.
+__device__ __forceinline__ int tile_order(unsigned block, int grid)
+{
+    const int xcd = block & 7, qq = grid >> 3, rr = grid & 7;
+    return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (block >> 3);
 }
 
 // n / d for 0 <= n < 2^24, 0 < d (float reciprocal estimate, then one correction step): a few VALU

@@ -155,9 +155,7 @@ __global__ __launch_bounds__(64 * kW_NW, 1) void conv3w_kernel(const ConvArgs a)
     const int ntm = (g.total + BM - 1) / BM;
     // XCD-aware bijective order of the persistent grid; block b walks m-tiles tix, tix + G, ...
     const int G = gridDim.x;
-    const int xcd = blockIdx.x & 7, qq = G >> 3, rr = G & 7;
-    const int tix = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (blockIdx.x >> 3);
-    int m = tix;
+    int m = tile_order(blockIdx.x, G);
     if (m >= ntm) return;
     if (OPKW_DESYNC > 0) {
         const unsigned long long d = (unsigned long long)(((blockIdx.x >> 3) % OPKW_DESYNC_N) * OPKW_DESYNC);

@@ -97,8 +97,7 @@ __global__ __launch_bounds__(64 * kH_NW, 1) void conv_head_kernel(const HeadArgs
     const int G = gridDim.x;
     int tile = blockIdx.x;
     if constexpr (PERSIST) {
-        const int xcd = blockIdx.x & 7, qq = G >> 3, rr = G & 7;
-        tile = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (blockIdx.x >> 3);
+        tile = tile_order(blockIdx.x, G);
         if (tile >= ntiles) return;
     }
 

@@ -1,6 +1,6 @@
 // conv_plan.cpp -- which kernel runs a 7x7 / 3x3 / 1x1 conv, on which tile, strips and grid: the
 // one decider behind NetHip's planner and frame runs, the launchers of conv3.hip, conv3w.hip,
-// conv3w8.hip and conv3s.hip, opk_net_conv_plan and opk_net_conv_kernels (conv.h).  Plain host
+// conv3w8.hip, opk_net_conv_plan and opk_net_conv_kernels (conv.h).  Plain host
 // code: no HIP calls, so the decision is testable without a GPU.
 #include "conv.h"
 

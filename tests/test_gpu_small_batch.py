@@ -1,4 +1,4 @@
-"""GPU: the small-batch net mode (Net.set_small_batch, conv3s.hip).
+"""GPU: the small-batch net mode (Net.set_small_batch, launch_conv3s in conv3.hip).
 
 With the mode on, 3x3 convs whose conv3_shape tiles give fewer workgroups than the chip has CUs run
 on conv3s_kernel's 64 x 32 / 128 x 64 tiles.  Every case first asserts from the launch log that

@@ -1,5 +1,5 @@
 """GPU: the small-batch net mode (Net.set_small_batch) on nets with 7x7 layers and a 3-pixel
-border -- conv3s_kernel's 7x7 instantiations and its 3x3 tiles at border 3 (conv3s.hip).
+border -- conv3s_kernel's 7x7 instantiations and its 3x3 tiles at border 3 (launch_conv3s in conv3.hip).
 
 Every case runs the mode off, then on, under LAUNCH_LOG=1; asserts from the log that conv3s_kernel
 ran for exactly the convs whose Net.conv_plan says small, on the plan's tile, and that one of them

@@ -8,7 +8,6 @@
 // plus the kernel's wall time from HIP events.  Inputs are random; only timing matters.
 #define OPK3_STAMPS
 #include "../openpose_amd/csrc/kernels/conv3.hip"
-#include "../openpose_amd/csrc/kernels/conv3s.hip"
 #include "../openpose_amd/csrc/kernels/conv3w.hip"
 #include "../openpose_amd/csrc/kernels/conv3w8.hip"
 #include "../openpose_amd/csrc/kernels/conv_plan.cpp"
