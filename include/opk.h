@@ -605,6 +605,64 @@ int opk_render_pose_distance(opk_ctx* ctx, float* frame_dev, unsigned width, uns
                              const float* heat_dev, int heat_w, int heat_h,
                              float scale_to_keep_ratio, unsigned part, float alpha);
 
+/* ---- The output image: the two stages around the renderers, and all three in one pass for a
+ *      batch of frames (enqueued on the context's stream).
+ * opk_cvmat_to_output replaces op::CvMatToOpOutput::createArray, CPU branch
+ *   (src/openpose/core/cvMatToOpOutput.cpp:76-149), for a batch: frames_dev = n BGR uint8 frames
+ *   [height][step bytes] (step 0 = width*3) -> output_dev float [n][out_h][out_w][3].
+ *   resizeFixedAspectRatio (openCvPrivate.cpp:34-53): cv::warpAffine(diag(scale)) with OpenCV's
+ *   fixed-point 8-bit arithmetic, INTER_CUBIC for scale > 1 else INTER_LINEAR, zero border; the
+ *   plain copy when scale == 1 and the sizes match.  Errors as the reference: "Output resolution
+ *   has 0 area.", "Input images has 0 area.".
+ * opk_output_to_cvmat replaces op::OpOutputToCvMat::formatToCvMat
+ *   (src/openpose/core/opOutputToCvMat.cpp:77-130) for a batch: float [n][h][w][3] -> uint8
+ *   [n][h][dst_step] (dst_step 0 = w*3; bytes of a row beyond w*3 are not written), with the cast
+ *   of its CPU branch or of its GPU branch. */
+#define OPK_CAST_CPU 0  /* cv::Mat::convertTo(CV_8UC3): saturate_cast<uchar>(cvRound(v)) -- round
+                           to nearest, ties to even, then clamp to [0, 255]                     */
+#define OPK_CAST_CUDA 1 /* uCharImageCast (gpu/cuda.cu:27-34): (uchar) fastTruncateCuda(v, 0,
+                           255) -- clamp, then truncate toward zero                             */
+int opk_cvmat_to_output(opk_ctx* ctx, float* output_dev, const uint8_t* frames_dev, int n,
+                        int width, int height, size_t step, double scale, int out_w, int out_h);
+int opk_output_to_cvmat(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, const float* output_dev,
+                        int n, int w, int h, int cast);
+
+/* One keypoint layer of opk_render_frames: what one of opk_render_pose_keypoints / _face_ /
+ * _hand_ would draw on each frame. */
+#define OPK_LAYER_POSE 0
+#define OPK_LAYER_FACE 1
+#define OPK_LAYER_HAND 2
+typedef struct opk_render_layer {
+    int kind;                   /* OPK_LAYER_*                                                 */
+    int pose_model;             /* POSE only                                                   */
+    const float* keypoints_dev; /* [sum(counts)][parts][3], frame 0's first, in output pixels  */
+    const int* counts_host;     /* [n]: people (faces, hands) of each frame                    */
+    float render_threshold, alpha;
+    int googly_eyes;            /* POSE only                                                   */
+} opk_render_layer;
+
+/* opk_render_frames: CvMatToOpOutput -> the layers in order -> OpOutputToCvMat for n frames in
+ *   one pass per pixel; the float image is never written to memory.  dst_dev uint8
+ *   [n][out_h][dst_step] (dst_step 0 = out_w*3).  blend_original == 0 clears each frame before the
+ *   first layer (renderPoseKeypointsGpu's blendOriginalFrame).  0..3 layers; with 0 layers this is
+ *   the warp + cast alone.  Per frame at most 127 people in a POSE layer (the reference's
+ *   POSE_MAX_PEOPLE error) and 1024 in a FACE / HAND layer.  The result bytes are exactly those of
+ *   opk_cvmat_to_output -> opk_render_*_keypoints per frame and layer -> opk_output_to_cvmat.
+ *   Argument errors (the renderers' texts) are raised before any device work; n == 0 succeeds
+ *   with none.
+ * opk_pose_render_frames: the last collected batch of a pose pipeline drawn on its frames: uploads
+ *   the batch's keypoints (x, y times scale_input_to_output) as one POSE layer of the pipeline's
+ *   model and calls opk_render_frames.  OPK_ERR_STATE when nothing is collected or n is not the
+ *   collected batch's frame count. */
+int opk_render_frames(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, int out_w, int out_h,
+                      const uint8_t* frames_dev, int n, int width, int height, size_t step,
+                      double scale_input_to_output, const opk_render_layer* layers, int n_layers,
+                      int blend_original, int cast);
+int opk_pose_render_frames(opk_pose* pose, uint8_t* dst_dev, size_t dst_step, int out_w, int out_h,
+                           const uint8_t* frames_dev, int n, int width, int height, size_t step,
+                           double scale_input_to_output, float render_threshold, float alpha,
+                           int googly_eyes, int blend_original, int cast);
+
 #ifdef __cplusplus
 }
 #endif

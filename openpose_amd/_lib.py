@@ -125,7 +125,20 @@ _SIGS = {
     "opk_pose_submit_frames": (_i, [_p, _p, _i, _i, _i, _c.c_size_t]),
     "opk_pose_forward_frames": (_i, [_p, _p, _i, _i, _i, _c.c_size_t]),
     "opk_pose_net_input": (_i, [_p, _i, _c.POINTER(_p), _ip, _ip]),
+    "opk_cvmat_to_output": (_i, [_p, _p, _p, _i, _i, _i, _c.c_size_t, _d, _i, _i]),
+    "opk_output_to_cvmat": (_i, [_p, _p, _c.c_size_t, _p, _i, _i, _i, _i]),
+    "opk_render_frames": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _i, _i, _i, _c.c_size_t, _d, _p, _i,
+                               _i, _i]),
+    "opk_pose_render_frames": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _i, _i, _i, _c.c_size_t, _d,
+                                    _f, _f, _i, _i, _i]),
 }
+
+
+class RenderLayerStruct(ctypes.Structure):
+    """opk_render_layer (include/opk.h)."""
+    _fields_ = [("kind", _i), ("pose_model", _i), ("keypoints_dev", _p), ("counts_host", _ip),
+                ("render_threshold", _f), ("alpha", _f), ("googly_eyes", _i)]
+
 
 _LIB = None
 

@@ -20,6 +20,30 @@ from .pose_tables import (BODY_25, CONNECT_CPU, CONNECT_GPU, CONNECT_INTER_MIN_A
 # heat-map semantics (include/opk.h OPK_MAPS_*): the reference's CPU build or its CUDA build
 MAPS_CPU, MAPS_CUDA = 0, 1
 PRECISION_FP16, PRECISION_SPLIT = 0, 1      # opk_net_set_precision
+CAST_CPU, CAST_CUDA = 0, 1                  # OpOutputToCvMat's branch (OPK_CAST_*)
+LAYER_POSE, LAYER_FACE, LAYER_HAND = 0, 1, 2   # opk_render_layer.kind (OPK_LAYER_*)
+# the renderers' default render threshold of each layer kind (alpha 0.6 for all)
+_LAYER_THRESHOLD = {LAYER_POSE: 0.05, LAYER_FACE: 0.4, LAYER_HAND: 0.2}
+
+
+class RenderLayer:
+    """One keypoint layer of Context.render_frames: keypoints float32 CUDA [sum(counts), parts, 3]
+    in output pixels, frame 0's people first (None when there are none); counts: people (faces,
+    hands) of each frame."""
+
+    def __init__(self, kind, keypoints, counts, threshold=None, alpha=0.6, pose_model=BODY_25,
+                 googly_eyes=False):
+        self.kind, self.keypoints, self.counts = kind, keypoints, list(counts)
+        self.threshold = _LAYER_THRESHOLD[kind] if threshold is None else threshold
+        self.alpha, self.pose_model, self.googly_eyes = alpha, pose_model, googly_eyes
+
+
+def _row_bytes(t, n, h, w):
+    """dst_step of a uint8 image batch: [n, h, w, 3], or [n, h, row bytes] with padded rows."""
+    assert t.dtype == torch.uint8 and t.is_contiguous() and t.shape[0] == n and t.shape[1] == h
+    step = t.shape[2] * 3 if t.dim() == 4 else t.shape[2]
+    assert (t.dim() == 3 or t.shape[3] == 3) and step >= w * 3
+    return step
 
 
 def _ptr(t):
@@ -196,6 +220,63 @@ class Context:
         else:
             check(self.L.opk_render_pose_paf(self.h, _ptr(frame), pose_model, w, h, _ptr(heat),
                                              heat.shape[-1], heat.shape[-2], scale, part, alpha))
+
+    # ---- the output image (CvMatToOpOutput / OpOutputToCvMat) and the fused batch render --------
+    def cvmat_to_output(self, frames, scale=1.0, out_size=None):
+        """op::CvMatToOpOutput for a batch: frames [n, h, w, 3] uint8 BGR (CUDA) -> float32
+        [n, out_h, out_w, 3]; out_size = (w, h), default the frames' own."""
+        n, h, w, c = frames.shape
+        assert c == 3 and frames.dtype == torch.uint8
+        ow, oh = out_size if out_size is not None else (w, h)
+        out = torch.empty((n, max(oh, 0), max(ow, 0), 3), dtype=torch.float32, device=frames.device)
+        check(self.L.opk_cvmat_to_output(self.h, _ptr(out), _ptr(frames), n, w, h, w * 3,
+                                         float(scale), ow, oh))
+        return out
+
+    def output_to_cvmat(self, output, cast=CAST_CPU, out=None):
+        """op::OpOutputToCvMat for a batch: float32 [n, h, w, 3] -> uint8 [n, h, w, 3] (or into the
+        rows of `out`, uint8 [n, h, row bytes >= w*3])."""
+        n, h, w, c = output.shape
+        assert c == 3 and output.dtype == torch.float32
+        if out is None:
+            out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=output.device)
+        check(self.L.opk_output_to_cvmat(self.h, _ptr(out), _row_bytes(out, n, h, w), _ptr(output),
+                                         n, w, h, cast))
+        return out
+
+    def render_frames(self, frames, layers, scale=1.0, out_size=None, blend_original=True,
+                      cast=CAST_CPU, out=None):
+        """CvMatToOpOutput -> the keypoint layers in order -> OpOutputToCvMat in one kernel:
+        frames [n, h, w, 3] uint8 BGR (CUDA), layers a list of RenderLayer -> uint8
+        [n, out_h, out_w, 3] (or into the rows of `out`, uint8 [n, out_h, row bytes])."""
+        n, h, w, c = frames.shape
+        assert c == 3 and frames.dtype == torch.uint8
+        ow, oh = out_size if out_size is not None else (w, h)
+        if out is None:
+            out = torch.empty((n, max(oh, 0), max(ow, 0), 3), dtype=torch.uint8,
+                              device=frames.device)
+        arr = (_lib.RenderLayerStruct * max(len(layers), 1))()
+        keep = []
+        for s, l in zip(arr, layers):
+            assert len(l.counts) == n, "one count per frame"
+            counts = (ctypes.c_int * max(n, 1))(*[int(v) for v in l.counts])
+            keep.append(counts)
+            parts = {LAYER_FACE: 70, LAYER_HAND: 21}.get(l.kind)
+            if parts is None and l.kind == LAYER_POSE and 0 <= l.pose_model <= 14:
+                parts = pose_model_info(l.pose_model)["parts"]
+            if l.keypoints is None:
+                assert sum(l.counts) == 0, "keypoints missing"
+            elif parts is not None:   # (an unknown kind or model is the library's error)
+                assert l.keypoints.dtype == torch.float32
+                assert tuple(l.keypoints.shape) == (sum(l.counts), parts, 3), "keypoints shape"
+            s.kind, s.pose_model = l.kind, l.pose_model
+            s.keypoints_dev = None if l.keypoints is None else _ptr(l.keypoints)
+            s.counts_host = counts
+            s.render_threshold, s.alpha, s.googly_eyes = l.threshold, l.alpha, int(l.googly_eyes)
+        check(self.L.opk_render_frames(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh,
+                                       _ptr(frames), n, w, h, w * 3, float(scale), arr, len(layers),
+                                       int(blend_original), cast))
+        return out
 
     def paf_scores(self, scores, heat, peaks, pose_model=BODY_25, inter_th=CONNECT_INTER_THRESHOLD,
                    inter_min_above=CONNECT_INTER_MIN_ABOVE_THRESHOLD, nms_th=NMS_THRESHOLD):
@@ -660,6 +741,20 @@ class PoseExtractor:
         check(self.L.opk_pose_keypoints(self.h, frame, kp.ctypes.data_as(ctypes.c_void_p),
                                         ks.ctypes.data_as(ctypes.c_void_p), n))
         return kp[:n], ks[:n]
+
+    def render_frames(self, frames, scale=1.0, out_size=None, threshold=0.05, alpha=0.6,
+                      googly_eyes=False, blend_original=True, cast=CAST_CPU, out=None):
+        """The last collected batch drawn on its frames [n, h, w, 3] uint8 BGR (CUDA) ->
+        uint8 [n, out_h, out_w, 3]; keypoints are scaled by `scale` (scaleInputToOutput)."""
+        n, h, w, c = frames.shape
+        assert c == 3 and frames.dtype == torch.uint8
+        ow, oh = out_size if out_size is not None else (w, h)
+        if out is None:
+            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
+        check(self.L.opk_pose_render_frames(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh,
+                                            _ptr(frames), n, w, h, w * 3, float(scale), threshold,
+                                            alpha, int(googly_eyes), int(blend_original), cast))
+        return out
 
     def set_timing(self, on=True):
         check(self.L.opk_pose_set_timing(self.h, int(on)))

@@ -506,6 +506,47 @@ int opk_pose_forward_frames(opk_pose* p, const uint8_t* frames, int n, int width
     });
 }
 
+int opk_pose_render_frames(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w, int out_h,
+                           const uint8_t* frames, int n, int width, int height, size_t step,
+                           double scale, float threshold, float alpha, int googly_eyes,
+                           int blend_original, int cast)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        std::vector<int> counts;
+        opk_render_layer layer{};
+        const opk::PoseHip& pose = *p->pose;
+        if (pose.frames() == 0) throw opk::Error(OPK_ERR_STATE, "no collected batch to render");
+        if (n != pose.frames())
+            throw opk::Error(OPK_ERR_STATE, "the collected batch has " +
+                                                std::to_string(pose.frames()) + " frames, not " +
+                                                std::to_string(n));
+        const int parts = opk::pose_model(pose.model()).parts;
+        std::vector<float> kp;
+        for (int f = 0; f < n; ++f) {
+            const int people = pose.num_people(f);
+            counts.push_back(people);
+            const auto& k = pose.keypoints(f);
+            kp.insert(kp.end(), k.begin(), k.begin() + (size_t)people * parts * 3);
+        }
+        // scaleKeypoints: x and y times scaleInputToOutput, in float
+        const float s = (float)scale;
+        if (s != 1.f)
+            for (size_t i = 0; i < kp.size(); i += 3) {
+                kp[i] *= s;
+                kp[i + 1] *= s;
+            }
+        layer.kind = OPK_LAYER_POSE;
+        layer.pose_model = pose.model();
+        layer.counts_host = counts.data();
+        layer.render_threshold = threshold;
+        layer.alpha = alpha;
+        layer.googly_eyes = googly_eyes;
+        opk::render_frames(p->ctx, dst, dst_step, out_w, out_h, frames, n, width, height, step,
+                           scale, &layer, 1, blend_original, cast, kp.data(), kp.size());
+    });
+}
+
 int opk_pose_net_input(opk_pose* p, int scale, const float** input_dev, int* net_w, int* net_h)
 {
     return guarded_net([&] {

@@ -11,6 +11,8 @@
 #include "../kernels/kernels.h"
 #include "pose_model.h"
 
+struct opk_render_layer;   // include/opk.h
+
 namespace opk {
 
 // OpenCV-style cubic tables for one (source size -> target size) axis (host/resize_tables.cpp)
@@ -46,6 +48,11 @@ struct Context {
     std::map<int, std::unique_ptr<RenderDev>> render_dev;
     const RenderDev& render_table(int which);
     DevBuf render_geom;
+    // opk_render_frames (its layers' geometry is in render_geom too): the layers' per-frame
+    // prefix offsets on the device and the host copy they were uploaded from (an unchanged batch
+    // layout is not uploaded again); the keypoints opk_pose_render_frames uploads
+    DevBuf frames_offsets, frames_keypoints;
+    std::vector<int> frames_offsets_host;
 
     DevBuf scratch_scores;   // dense pair scores for opk_connect_body_parts
     // NMS candidate lists (nms.hip), zeroed when (re)allocated; the kernels keep them zeroed
@@ -73,6 +80,13 @@ struct Context {
         OPK_HIP(hipSetDevice(device));
     }
 };
+
+// opk_render_frames (host/render.cpp).  kp_host (may be NULL): layer 0's kp_floats keypoint values
+// still on the host (opk_pose_render_frames); they are uploaded after the argument checks.
+void render_frames(Context* ctx, uint8_t* dst, size_t dst_step, int out_w, int out_h,
+                   const uint8_t* frames, int n, int width, int height, size_t step, double scale,
+                   const ::opk_render_layer* layers, int n_layers, int blend_original, int cast,
+                   const float* kp_host = nullptr, size_t kp_floats = 0);
 
 // Device-time measurement hook (no reference counterpart): while enabled, begin()/end() bracket a
 // region of stream work with a pair of HIP events; read() waits for every recorded pair and

@@ -5,6 +5,7 @@
 // texts; the scratch pointers of the reference signatures (maxPtr / minPtr / scalePtr) are not
 // needed: the per-person boxes live in the context's own scratch (kernels/render.hip).
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -149,6 +150,175 @@ const Context::RenderDev& Context::render_table(int which)
     return ref;
 }
 
+namespace {
+
+// ---- the output image (CvMatToOpOutput, OpOutputToCvMat) and the fused batch render -------------
+
+void check_output_sizes(int width, int height, int out_w, int out_h, size_t step, double scale)
+{
+    // CvMatToOpOutput::createArray's sanity checks (cvMatToOpOutput.cpp:87-90)
+    OPK_CHECK_ARG(width > 0 && height > 0, "Input images has 0 area.");
+    OPK_CHECK_ARG(out_w > 0 && out_h > 0, "Output resolution has 0 area.");
+    OPK_CHECK_ARG(step == 0 || step >= (size_t)width * 3, "row step shorter than the row");
+    OPK_CHECK_ARG(scale > 0 && std::isfinite(scale), "scale must be positive");
+}
+
+void check_cast(int cast)
+{
+    OPK_CHECK_ARG(cast == OPK_CAST_CPU || cast == OPK_CAST_CUDA,
+                  "cast: OPK_CAST_CPU (0) or OPK_CAST_CUDA (1)");
+}
+
+// resizeFixedAspectRatio (openCvPrivate.cpp:34-53): the copy when nothing changes, else
+// cv::warpAffine(diag(scale)) with the tables of the net-input warp (host/input.cpp)
+FrameWarp frame_warp(Context* ctx, const uint8_t* frames, int width, int height, size_t step,
+                     double scale, int out_w, int out_h)
+{
+    FrameWarp wp{};
+    wp.src = frames;
+    wp.src_step = step ? step : (size_t)width * 3;
+    wp.sw = width;
+    wp.sh = height;
+    if (scale != 1. || out_w != width || out_h != height) {
+        const bool cubic = scale > 1.;
+        const auto& ax = ctx->warp_axis_tables(scale, out_w, out_h);
+        wp.xtab = ax.x;
+        wp.ytab = ax.y;
+        wp.wtab = ctx->warp_weight_table(cubic);
+        wp.ksize = cubic ? 4 : 2;
+    }
+    return wp;
+}
+
+// what renderPoseKeypointsGpu / renderFaceKeypointsGpu / renderHandKeypointsGpu fix for a layer
+struct LayerRender {
+    int table, scales_table, parts, eye1, eye2, max_people;
+    float radius_div, line_div;
+};
+
+LayerRender layer_render(const opk_render_layer& l)
+{
+    check_alpha(l.alpha);
+    if (l.kind == OPK_LAYER_FACE) return {kRtFace, kRtFace, 70, -1, -1, kRenderMaxPeople, 120.f, 250.f};
+    if (l.kind == OPK_LAYER_HAND) return {kRtHand, kRtHand, 21, -1, -1, kRenderMaxPeople, 100.f, 80.f};
+    OPK_CHECK_ARG(l.kind == OPK_LAYER_POSE, "unknown layer kind");
+    PoseRender pr{};
+    const bool known = pose_render(l.pose_model, &pr);
+    OPK_CHECK_ARG(!(l.googly_eyes && (l.pose_model == 2 || l.pose_model == 3)),
+                  "Bool googlyEyes not compatible with MPI models.");
+    OPK_CHECK_ARG(known, "Invalid Model.");
+    return {pr.table, pr.scales_table, pr.parts, l.googly_eyes ? pr.eye1 : -1,
+            l.googly_eyes ? pr.eye2 : -1, 127, 100.f, 120.f};
+}
+
+}  // namespace
+
+void render_frames(Context* ctx, uint8_t* dst, size_t dst_step, int out_w, int out_h,
+                   const uint8_t* frames, int n, int width, int height, size_t step, double scale,
+                   const opk_render_layer* layers, int n_layers, int blend_original, int cast,
+                   const float* kp_host, size_t kp_floats)
+{
+    // everything that does not depend on the frames first, then each frame's counts; device work
+    // starts only after the last check
+    OPK_CHECK_ARG(n >= 0, "negative frame count");
+    OPK_CHECK_ARG(n_layers >= 0 && n_layers <= kRenderMaxLayers, "at most 3 layers");
+    OPK_CHECK_ARG(n_layers == 0 || layers, "NULL layers");
+    check_cast(cast);
+    check_output_sizes(width, height, out_w, out_h, step, scale);
+    OPK_CHECK_ARG(dst_step == 0 || dst_step >= (size_t)out_w * 3, "row step shorter than the row");
+    LayerRender lr[kRenderMaxLayers];
+    for (int l = 0; l < n_layers; ++l) lr[l] = layer_render(layers[l]);
+    if (n == 0) return;
+    OPK_CHECK_ARG(dst && frames, "NULL buffer");
+    // prefix offsets of every layer: [n_layers][n + 1]
+    std::vector<int> offsets((size_t)n_layers * (n + 1));
+    size_t geom_floats = 0, geom_at[kRenderMaxLayers] = {};
+    for (int l = 0; l < n_layers; ++l) {
+        OPK_CHECK_ARG(layers[l].counts_host, "NULL counts");
+        int* off = offsets.data() + (size_t)l * (n + 1);
+        off[0] = 0;
+        for (int f = 0; f < n; ++f) {
+            const int c = layers[l].counts_host[f];
+            OPK_CHECK_ARG(c >= 0, "negative count");
+            if (layers[l].kind == OPK_LAYER_POSE)
+                OPK_CHECK_ARG(c <= 127,
+                              "Rendering assumes that numberPeople <= POSE_MAX_PEOPLE = 127.");
+            OPK_CHECK_ARG(c <= lr[l].max_people,
+                          "at most " + std::to_string(kRenderMaxPeople) + " people per frame");
+            OPK_CHECK_ARG(off[f] <= (1 << 24) - c, "too many people in the batch");
+            off[f + 1] = off[f] + c;
+        }
+        if (l == 0 && kp_host)
+            OPK_CHECK_ARG(kp_floats == (size_t)off[n] * lr[l].parts * 3, "keypoint count");
+        else
+            OPK_CHECK_ARG(off[n] == 0 || layers[l].keypoints_dev, "NULL keypoints");
+        geom_at[l] = geom_floats;
+        const auto& row = kRenderTableRows[lr[l].table];
+        geom_floats += render_geom_floats(off[n], lr[l].parts, row.npairs);
+    }
+
+    ctx->bind();
+    RenderFramesArgs a{};
+    a.dst = dst;
+    a.dst_step = dst_step ? dst_step : (size_t)out_w * 3;
+    a.w = out_w;
+    a.h = out_h;
+    a.n = n;
+    a.warp = frame_warp(ctx, frames, width, height, step, scale, out_w, out_h);
+    a.blend = blend_original ? 1 : 0;
+    a.cast = cast;
+    a.nlayers = n_layers;
+    if (n_layers > 0) {
+        int* dev = static_cast<int*>(ctx->frames_offsets.get(offsets.size() * sizeof(int)));
+        if (offsets != ctx->frames_offsets_host) {
+            OPK_HIP(hipMemcpyAsync(dev, offsets.data(), offsets.size() * sizeof(int),
+                                   hipMemcpyHostToDevice, ctx->stream));
+            OPK_HIP(hipStreamSynchronize(ctx->stream));
+            ctx->frames_offsets_host = offsets;
+        }
+        float* geom = static_cast<float*>(
+            ctx->render_geom.get(std::max<size_t>(1, geom_floats) * sizeof(float)));
+        const int m = out_w < out_h ? out_w : out_h;
+        for (int l = 0; l < n_layers; ++l) {
+            const auto& t = ctx->render_table(lr[l].table);
+            const auto& st = ctx->render_table(lr[l].scales_table);
+            const int total = offsets[(size_t)l * (n + 1) + n];
+            // one geometry pass over the layer's people of every frame, with the arguments
+            // render_keypoints gives the per-frame renderers
+            RenderKeypointsArgs p{};
+            p.w = out_w;
+            p.h = out_h;
+            p.kp = layers[l].keypoints_dev;
+            if (l == 0 && kp_host && kp_floats > 0) {
+                void* kd = ctx->frames_keypoints.get(kp_floats * sizeof(float));
+                OPK_HIP(hipMemcpyAsync(kd, kp_host, kp_floats * sizeof(float),
+                                       hipMemcpyHostToDevice, ctx->stream));
+                OPK_HIP(hipStreamSynchronize(ctx->stream));
+                p.kp = static_cast<const float*>(kd);
+            }
+            p.people = total;
+            p.parts = lr[l].parts;
+            p.pairs = t.pairs;
+            p.npairs = t.npairs;
+            p.colors = t.colors;
+            p.ncolors = t.ncolors;
+            p.scales = st.scales;
+            p.nscales = t.nscales;
+            p.radius = (float)m / lr[l].radius_div;
+            p.line_width = (float)m / lr[l].line_div;
+            p.threshold = layers[l].render_threshold;
+            p.alpha = layers[l].alpha;
+            p.eye1 = lr[l].eye1;
+            p.eye2 = lr[l].eye2;
+            p.geom = geom + geom_at[l];
+            launch_render_prep(p, ctx->stream);
+            a.layer[l] = RenderFramesLayer{p.geom, dev + (size_t)l * (n + 1), total, p.parts,
+                                           p.npairs, p.colors, p.alpha};
+        }
+    }
+    launch_render_frames(a, ctx->stream);
+}
+
 }  // namespace opk
 
 struct opk_ctx : opk::Context {};
@@ -268,6 +438,52 @@ int opk_render_pose_distance(opk_ctx* ctx, float* frame, unsigned width, unsigne
         ctx->bind();
         // renderPoseDistanceGpu (renderPose.cu:836-864): renderBodyPartHeatMap with absValue
         opk::launch_render_heat_map(a, (int)part, true, ctx->stream);
+    });
+}
+
+int opk_cvmat_to_output(opk_ctx* ctx, float* output_dev, const uint8_t* frames_dev, int n, int width,
+                        int height, size_t step, double scale, int out_w, int out_h)
+{
+    return opk::guarded_render([&] {
+        OPK_CHECK_ARG(ctx != nullptr, "NULL argument");
+        OPK_CHECK_ARG(n >= 0, "negative frame count");
+        opk::check_output_sizes(width, height, out_w, out_h, step, scale);
+        if (n == 0) return;
+        OPK_CHECK_ARG(output_dev && frames_dev, "NULL buffer");
+        ctx->bind();
+        opk::launch_cvmat_to_output(
+            output_dev, n, out_w, out_h,
+            opk::frame_warp(ctx, frames_dev, width, height, step, scale, out_w, out_h),
+            ctx->stream);
+    });
+}
+
+int opk_output_to_cvmat(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, const float* output_dev,
+                        int n, int w, int h, int cast)
+{
+    return opk::guarded_render([&] {
+        OPK_CHECK_ARG(ctx != nullptr, "NULL argument");
+        OPK_CHECK_ARG(n >= 0, "negative frame count");
+        opk::check_cast(cast);
+        OPK_CHECK_ARG(w > 0 && h > 0, "Output resolution has 0 area.");
+        OPK_CHECK_ARG(dst_step == 0 || dst_step >= (size_t)w * 3, "row step shorter than the row");
+        if (n == 0) return;
+        OPK_CHECK_ARG(dst_dev && output_dev, "NULL buffer");
+        ctx->bind();
+        opk::launch_output_to_cvmat(dst_dev, dst_step ? dst_step : (size_t)w * 3, output_dev, n, w,
+                                    h, cast, ctx->stream);
+    });
+}
+
+int opk_render_frames(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, int out_w, int out_h,
+                      const uint8_t* frames_dev, int n, int width, int height, size_t step,
+                      double scale_input_to_output, const opk_render_layer* layers, int n_layers,
+                      int blend_original, int cast)
+{
+    return opk::guarded_render([&] {
+        OPK_CHECK_ARG(ctx != nullptr, "NULL argument");
+        opk::render_frames(ctx, dst_dev, dst_step, out_w, out_h, frames_dev, n, width, height,
+                           step, scale_input_to_output, layers, n_layers, blend_original, cast);
     });
 }
 

@@ -122,6 +122,50 @@ struct RenderKeypointsArgs {
 };
 size_t render_geom_floats(int people, int parts, int npairs);
 void launch_render_keypoints(const RenderKeypointsArgs& a, hipStream_t stream);
+// the geometry pass alone (a.people may be the people of many frames, frame 0's first: nothing in
+// a person's geometry depends on the frame it is drawn on); a.frame is not touched
+void launch_render_prep(const RenderKeypointsArgs& a, hipStream_t stream);
+
+// ---- output image: CvMatToOpOutput / OpOutputToCvMat and the fused batch render (render.hip) ----
+// The warp of n BGR uint8 frames [sh][src_step] (frame stride src_step * sh) to w x h pixels:
+// ksize 2 / 4 with the tables of launch_cvmat_to_input, or 0 for the plain copy (then w, h = sw, sh)
+struct FrameWarp {
+    const uint8_t* src;
+    size_t src_step;
+    int sw, sh;
+    const int* xtab;
+    const int* ytab;
+    const short* wtab;
+    int ksize;
+};
+// dst float BGR [n][h][w][3]
+void launch_cvmat_to_output(float* dst, int n, int w, int h, const FrameWarp& warp,
+                            hipStream_t stream);
+// dst uint8 [n][h][dst_step] (only w*3 bytes of a row are written) from src float [n][h][w][3];
+// cast 0: cvRound + saturate (cv::Mat::convertTo), 1: clamp + truncate (uCharImageCast)
+void launch_output_to_cvmat(uint8_t* dst, size_t dst_step, const float* src, int n, int w, int h,
+                            int cast, hipStream_t stream);
+// One keypoint layer of the fused render: geometry (launch_render_prep's layout over `total`
+// people) and the device prefix offsets [n + 1] of each frame's people in it
+struct RenderFramesLayer {
+    const float* geom;
+    const int* offsets;
+    int total, parts, npairs;
+    const float* colors;
+    float alpha;
+};
+constexpr int kRenderMaxLayers = 3;
+struct RenderFramesArgs {
+    uint8_t* dst;
+    size_t dst_step;
+    int w, h, n;
+    FrameWarp warp;
+    int blend, cast, nlayers;
+    int dst_aligned;   // set by the launcher: dst and dst_step are multiples of 4
+    RenderFramesLayer layer[kRenderMaxLayers];
+};
+// warp -> every layer in order -> cast, one pass per pixel
+void launch_render_frames(const RenderFramesArgs& a, hipStream_t stream);
 // heat-map renders: frame [h][w][3] BGR; heat [channels][hh][hw]; target pixel x samples the heat
 // map at (x + 0.5) / scale - 0.5
 struct RenderHeatArgs {

@@ -30,6 +30,7 @@
 // from the CUDA build's: that part of render parity is unpinned.
 #include "kernels.h"
 #include "heat_dev.h"
+#include "warp_dev.h"
 #include "../common.h"
 
 namespace opk {
@@ -58,9 +59,8 @@ __device__ __forceinline__ void blend(float& r, float& g, float& b, float cr, fl
 
 // one wave per person: box (a lane-strided scan + wave reduction; min / max do not depend on the
 // order), then lanes take limbs and parts
-__global__ __launch_bounds__(64) void render_prep_kernel(RenderKeypointsArgs a)
+__device__ __forceinline__ void render_prep_person(const RenderKeypointsArgs& a, int p, int lane)
 {
-    const int p = blockIdx.x, lane = threadIdx.x;
     const float* kp = a.kp + (size_t)p * a.parts * 3;
     float* box = a.geom + (size_t)p * 8;
     float* limb = a.geom + (size_t)a.people * 8 + (size_t)p * a.npairs * 8;
@@ -155,6 +155,13 @@ __global__ __launch_bounds__(64) void render_prep_kernel(RenderKeypointsArgs a)
     }
 }
 
+// a.people may span many frames (the batched render): a person's geometry does not depend on the
+// frame, whose slice of people the draw kernel takes from the prefix offsets
+__global__ __launch_bounds__(64) void render_prep_kernel(RenderKeypointsArgs a)
+{
+    render_prep_person(a, blockIdx.x, threadIdx.x);
+}
+
 // squared distance from (cx, cy) to the tile's pixel rectangle, with the per-pixel test's own
 // operations at its nearest pixel: never above any pixel's dist^2 (rounding is monotonic)
 __device__ __forceinline__ float rect_d2(float cx, float cy, float fx0, float fy0, float fx1,
@@ -182,18 +189,58 @@ __device__ __forceinline__ int compact(bool hit, int* wcount, int* total)
     return hit ? off + __popcll(m & ((1ull << lane) - 1ull)) : -1;
 }
 
-__global__ __launch_bounds__(256) void render_keypoints_kernel(RenderKeypointsArgs a)
+// One keypoint render's people as the draw stages see them: `people` consecutive persons of a
+// geometry buffer (render_prep_person's layout), their colors and the blend weight.
+struct RenderView {
+    const float* boxes;     // [people][8]
+    const float* limbs;     // [people][npairs][8]
+    const float* circles;   // [people][parts][8]
+    const float* colors;
+    int people, npairs, parts;
+    float alpha;
+};
+// `people` persons from person `first` of a geometry buffer that holds `total`
+__device__ __forceinline__ RenderView render_view(const float* geom, int total, int first,
+                                                  int people, int npairs, int parts,
+                                                  const float* colors, float alpha)
 {
-    __shared__ unsigned short plist[kRenderMaxPeople];
-    // one round's drawable items in draw order: {box}, {geometry}, {geometry, type, color}
-    __shared__ float4 items[256][4];
-    __shared__ int wcount[4];
+    const float* limbs = geom + (size_t)total * 8;
+    const float* circles = limbs + (size_t)total * npairs * 8;
+    return RenderView{geom + (size_t)first * 8, limbs + (size_t)first * npairs * 8,
+                      circles + (size_t)first * parts * 8, colors, people, npairs, parts, alpha};
+}
+
+// The workgroup's 32x8 pixel tile and this thread's pixel of it
+struct RenderTile {
+    float fx0, fy0, fx1, fy1;   // the tile's pixel rectangle, clipped to the frame
+    int x, y;
+    bool inside;
+};
+__device__ __forceinline__ RenderTile render_tile(int w, int h)
+{
     const int tx0 = blockIdx.x * kTileW, ty0 = blockIdx.y * kTileH;
-    const float fx0 = (float)tx0, fy0 = (float)ty0;
-    const float fx1 = (float)min(tx0 + kTileW - 1, a.w - 1), fy1 = (float)min(ty0 + kTileH - 1, a.h - 1);
-    const float* __restrict__ boxes = a.geom;
-    const float* __restrict__ limbs = a.geom + (size_t)a.people * 8;
-    const float* __restrict__ circles = limbs + (size_t)a.people * a.npairs * 8;
+    RenderTile t;
+    t.fx0 = (float)tx0;
+    t.fy0 = (float)ty0;
+    t.fx1 = (float)min(tx0 + kTileW - 1, w - 1);
+    t.fy1 = (float)min(ty0 + kTileH - 1, h - 1);
+    t.x = tx0 + (threadIdx.x & (kTileW - 1));
+    t.y = ty0 + threadIdx.x / kTileW;
+    t.inside = t.x < w && t.y < h;
+    return t;
+}
+
+// Stages 1 and 2 of the header comment for one view on the thread's pixel (b, g, r); every thread
+// of the 256-thread workgroup calls it (barriers inside).  LDS: plist [kRenderMaxPeople], one
+// round's drawable items in draw order -- {box}, {geometry}, {geometry, type, color} --, wcount [4].
+__device__ __forceinline__ void render_view_pixel(const RenderView& a, const RenderTile& t,
+                                                  unsigned short* plist, float4 (*items)[4],
+                                                  int* wcount, float& b, float& g, float& r)
+{
+    const float fx0 = t.fx0, fy0 = t.fy0, fx1 = t.fx1, fy1 = t.fy1;
+    const float* __restrict__ boxes = a.boxes;
+    const float* __restrict__ limbs = a.limbs;
+    const float* __restrict__ circles = a.circles;
     const float* __restrict__ colors = a.colors;
 
     // 1. the people whose box meets this tile, in person order
@@ -212,16 +259,9 @@ __global__ __launch_bounds__(256) void render_keypoints_kernel(RenderKeypointsAr
         n += tot;
     }
 
-    const int x = tx0 + (threadIdx.x & (kTileW - 1)), y = ty0 + threadIdx.x / kTileW;
-    const bool inside = x < a.w && y < a.h;
-    const size_t base = 3 * ((size_t)(inside ? y : 0) * a.w + (inside ? x : 0));
-    float b = 0.f, g = 0.f, r = 0.f;
-    if (inside && a.blend) {
-        b = a.frame[base];
-        g = a.frame[base + 1];
-        r = a.frame[base + 2];
-    }
-    const float fx = (float)x, fy = (float)y;
+    const int x = t.x;
+    const bool inside = t.inside;
+    const float fx = (float)t.x, fy = (float)t.y;
 
     // 2. rounds of 256 (person, limb | part) candidates, person-major, limbs before parts (the
     //    reference's draw order); those whose ellipse bound / circle reaches the tile go to LDS
@@ -300,10 +340,155 @@ __global__ __launch_bounds__(256) void render_keypoints_kernel(RenderKeypointsAr
         }
         __syncthreads();   // the next round rewrites items
     }
-    if (inside) {
+}
+
+__global__ __launch_bounds__(256) void render_keypoints_kernel(RenderKeypointsArgs a)
+{
+    __shared__ unsigned short plist[kRenderMaxPeople];
+    __shared__ float4 items[256][4];
+    __shared__ int wcount[4];
+    const RenderTile t = render_tile(a.w, a.h);
+    const size_t base = 3 * ((size_t)(t.inside ? t.y : 0) * a.w + (t.inside ? t.x : 0));
+    float b = 0.f, g = 0.f, r = 0.f;
+    if (t.inside && a.blend) {
+        b = a.frame[base];
+        g = a.frame[base + 1];
+        r = a.frame[base + 2];
+    }
+    render_view_pixel(render_view(a.geom, a.people, 0, a.people, a.npairs, a.parts, a.colors,
+                                  a.alpha),
+                      t, plist, items, wcount, b, g, r);
+    if (t.inside) {
         a.frame[base] = b;
         a.frame[base + 1] = g;
         a.frame[base + 2] = r;
+    }
+}
+
+// ---- the output image: CvMatToOpOutput, OpOutputToCvMat and the fused batch render ---------------
+
+// this thread's pixel of frame f as CvMatToOpOutput's warp (or copy, K == 0) gives it
+template <int K>
+__device__ __forceinline__ void output_pixel(int u[3], const FrameWarp& wp, int f, int x, int y)
+{
+    const uint8_t* fsrc = wp.src + (size_t)f * wp.src_step * wp.sh;
+    if constexpr (K == 0) {
+        const uint8_t* p = fsrc + (size_t)y * wp.src_step + (size_t)x * 3;
+        u[0] = p[0];
+        u[1] = p[1];
+        u[2] = p[2];
+    } else {
+        const int2 xt = reinterpret_cast<const int2*>(wp.xtab)[x];
+        const int2 yt = reinterpret_cast<const int2*>(wp.ytab)[y];
+        const size_t step = wp.src_step;
+        warp_pixel<K>(u, yt, xt, warp_weights<K>(wp.wtab, yt.y, xt.y), wp.sh, wp.sw,
+                      [&](int, int yy) { return fsrc + (size_t)yy * step; });
+    }
+}
+
+// OpOutputToCvMat's two casts of one value
+__device__ __forceinline__ unsigned cast_u8(float v, int cast)
+{
+    if (cast == 0) {   // saturate_cast<uchar>(cvRound(v)): ties to even, then clamp
+        const int i = __float2int_rn(v);
+        return (unsigned)(i < 0 ? 0 : (i > 255 ? 255 : i));
+    }
+    return (unsigned)(int)truncate_ref(v, 0.f, 255.f);   // uCharImageCast (cuda.cu:27-34)
+}
+
+// one thread per output pixel, all three channels
+template <int K>
+__global__ __launch_bounds__(256) void cvmat_to_output_kernel(float* __restrict__ dst, int w, int h,
+                                                              FrameWarp wp)
+{
+    const RenderTile t = render_tile(w, h);
+    if (!t.inside) return;
+    int u[3];
+    output_pixel<K>(u, wp, blockIdx.z, t.x, t.y);
+    float* o = dst + 3 * (((size_t)blockIdx.z * h + t.y) * w + t.x);
+    o[0] = (float)u[0];
+    o[1] = (float)u[1];
+    o[2] = (float)u[2];
+}
+
+// rows of w*3 values; V: four values per thread (one 16-byte load, one 4-byte store) when every
+// row of both arrays starts on such a boundary, else one value per thread
+template <bool V>
+__global__ __launch_bounds__(256) void output_to_cvmat_kernel(uint8_t* __restrict__ dst,
+                                                              size_t dst_step,
+                                                              const float* __restrict__ src,
+                                                              int row_values, int h, int cast)
+{
+    const int i = (blockIdx.x * 256 + threadIdx.x) * (V ? 4 : 1);
+    if (i >= row_values) return;   // V: row_values is a multiple of 4
+    const size_t row = (size_t)blockIdx.z * h + blockIdx.y;
+    const float* s = src + row * row_values + i;
+    uint8_t* d = dst + row * dst_step + i;
+    if (V) {
+        const float4 v = *reinterpret_cast<const float4*>(s);
+        *reinterpret_cast<unsigned*>(d) = cast_u8(v.x, cast) | cast_u8(v.y, cast) << 8 |
+                                          cast_u8(v.z, cast) << 16 | cast_u8(v.w, cast) << 24;
+    } else {
+        *d = (uint8_t)cast_u8(*s, cast);
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void render_frames_kernel(RenderFramesArgs a)
+{
+    __shared__ unsigned short plist[kRenderMaxPeople];
+    __shared__ float4 items[256][4];
+    __shared__ int wcount[4];
+    const int f = blockIdx.z;
+    const RenderTile t = render_tile(a.w, a.h);
+    // 1. the pixel of the output image, in registers from here to the store
+    float b = 0.f, g = 0.f, r = 0.f;
+    if (t.inside && a.blend) {
+        int u[3];
+        output_pixel<K>(u, a.warp, f, t.x, t.y);
+        b = (float)u[0];
+        g = (float)u[1];
+        r = (float)u[2];
+    }
+    // 2. every layer in order on the frame's own people
+    for (int l = 0; l < a.nlayers; ++l) {
+        const RenderFramesLayer& L = a.layer[l];
+        const int first = L.offsets[f], people = L.offsets[f + 1] - first;
+        render_view_pixel(render_view(L.geom, L.total, first, people, L.npairs, L.parts, L.colors,
+                                      L.alpha),
+                          t, plist, items, wcount, b, g, r);
+    }
+    // 3. OpOutputToCvMat's cast
+    const unsigned cb = cast_u8(b, a.cast), cg = cast_u8(g, a.cast), cr = cast_u8(r, a.cast);
+    if (!a.dst_aligned) {
+        if (t.inside) {
+            uint8_t* d = a.dst + ((size_t)f * a.h + t.y) * a.dst_step + (size_t)t.x * 3;
+            d[0] = (uint8_t)cb;
+            d[1] = (uint8_t)cg;
+            d[2] = (uint8_t)cr;
+        }
+        return;
+    }
+    // rows on 4-byte boundaries (a tile starts at byte 96 * blockIdx.x of its rows): the tile's
+    // 8 x 96 bytes go through LDS -- `items` is idle, every use of it ended at a barrier -- and
+    // leave as 4-byte stores, 24 lanes a row; a row's last 1..3 bytes, if any, as bytes
+    uint8_t* stage = reinterpret_cast<uint8_t*>(items);
+    uint8_t* mine = stage + threadIdx.x * 3;   // (threadIdx.x / 32) * 96 + (threadIdx.x % 32) * 3
+    mine[0] = (uint8_t)cb;
+    mine[1] = (uint8_t)cg;
+    mine[2] = (uint8_t)cr;
+    __syncthreads();
+    const int tx0 = blockIdx.x * kTileW, ty0 = blockIdx.y * kTileH;
+    const int rows = min(kTileH, a.h - ty0), row_bytes = min(kTileW, a.w - tx0) * 3;
+    const int row = threadIdx.x / 24, o = (threadIdx.x % 24) * 4;
+    if (row < rows && o < row_bytes) {   // row < 8 only for threadIdx.x < 192
+        uint8_t* d = a.dst + ((size_t)f * a.h + ty0 + row) * a.dst_step + (size_t)tx0 * 3 + o;
+        const uint8_t* s = stage + row * (kTileW * 3) + o;
+        if (o + 4 <= row_bytes) {
+            *reinterpret_cast<unsigned*>(d) = *reinterpret_cast<const unsigned*>(s);
+        } else {
+            for (int i = 0; i < row_bytes - o; ++i) d[i] = s[i];
+        }
     }
 }
 
@@ -467,14 +652,101 @@ size_t render_geom_floats(int people, int parts, int npairs)
     return (size_t)people * (8 + (size_t)npairs * 8 + (size_t)parts * 8);
 }
 
+void launch_render_prep(const RenderKeypointsArgs& a, hipStream_t stream)
+{
+    if (a.people <= 0) return;
+    render_prep_kernel<<<a.people, 64, 0, stream>>>(a);
+    OPK_LAUNCH_CHECK();
+}
+
 void launch_render_keypoints(const RenderKeypointsArgs& a, hipStream_t stream)
 {
     if (a.w <= 0 || a.h <= 0) return;
-    if (a.people > 0) {
-        render_prep_kernel<<<a.people, 64, 0, stream>>>(a);
-        OPK_LAUNCH_CHECK();
-    }
+    launch_render_prep(a, stream);
     render_keypoints_kernel<<<tiles(a.w, a.h), kTileW * kTileH, 0, stream>>>(a);
+    OPK_LAUNCH_CHECK();
+}
+
+namespace {
+
+// the (tiles_x, tiles_y, n) grid of the batch kernels
+dim3 batch_tiles(int w, int h, int n)
+{
+    dim3 g = tiles(w, h);
+    OPK_CHECK_ARG(g.y <= 65535u && n <= 65535, "more than 65535 tile rows or frames");
+    g.z = (unsigned)n;
+    return g;
+}
+
+void check_warp(const FrameWarp& wp, int w, int h)
+{
+    OPK_CHECK_ARG(wp.src && wp.sw > 0 && wp.sh > 0, "empty frame");
+    OPK_CHECK_ARG(wp.src_step >= (size_t)wp.sw * 3, "row step shorter than the row");
+    OPK_CHECK_ARG(wp.ksize == 0 || wp.ksize == 2 || wp.ksize == 4, "copy, linear or cubic");
+    OPK_CHECK_ARG(wp.ksize != 0 || (w == wp.sw && h == wp.sh), "a copy keeps the size");
+    OPK_CHECK_ARG(wp.ksize == 0 || (wp.xtab && wp.ytab && wp.wtab), "NULL warp table");
+}
+
+}  // namespace
+
+void launch_cvmat_to_output(float* dst, int n, int w, int h, const FrameWarp& wp,
+                            hipStream_t stream)
+{
+    OPK_CHECK_ARG(dst && n > 0 && w > 0 && h > 0, "empty output image");
+    check_warp(wp, w, h);
+    const dim3 grid = batch_tiles(w, h, n), block(kTileW * kTileH);
+    if (wp.ksize == 0)
+        hipLaunchKernelGGL(cvmat_to_output_kernel<0>, grid, block, 0, stream, dst, w, h, wp);
+    else if (wp.ksize == 2)
+        hipLaunchKernelGGL(cvmat_to_output_kernel<2>, grid, block, 0, stream, dst, w, h, wp);
+    else
+        hipLaunchKernelGGL(cvmat_to_output_kernel<4>, grid, block, 0, stream, dst, w, h, wp);
+    OPK_LAUNCH_CHECK();
+}
+
+void launch_output_to_cvmat(uint8_t* dst, size_t dst_step, const float* src, int n, int w, int h,
+                            int cast, hipStream_t stream)
+{
+    OPK_CHECK_ARG(dst && src && n > 0 && w > 0 && h > 0, "empty output image");
+    OPK_CHECK_ARG(w <= (1 << 29) / 3, "row too long");
+    OPK_CHECK_ARG(dst_step >= (size_t)w * 3, "row step shorter than the row");
+    OPK_CHECK_ARG(cast == 0 || cast == 1, "unknown cast");
+    OPK_CHECK_ARG(h <= 65535 && n <= 65535, "more than 65535 rows or frames");
+    const int row = w * 3;
+    // four values per thread: a row of floats starts 16-byte aligned when w*3 is a multiple of
+    // 4, a row of bytes 4-byte aligned when dst_step is; the last store ends at w*3 exactly
+    const bool vec = row % 4 == 0 && dst_step % 4 == 0 && (uintptr_t)dst % 4 == 0 &&
+                     (uintptr_t)src % 16 == 0;
+    const int per_block = 256 * (vec ? 4 : 1);
+    const dim3 grid((unsigned)((row + per_block - 1) / per_block), (unsigned)h, (unsigned)n);
+    if (vec)
+        hipLaunchKernelGGL(output_to_cvmat_kernel<true>, grid, dim3(256), 0, stream, dst, dst_step,
+                           src, row, h, cast);
+    else
+        hipLaunchKernelGGL(output_to_cvmat_kernel<false>, grid, dim3(256), 0, stream, dst,
+                           dst_step, src, row, h, cast);
+    OPK_LAUNCH_CHECK();
+}
+
+void launch_render_frames(const RenderFramesArgs& args, hipStream_t stream)
+{
+    RenderFramesArgs a = args;
+    a.dst_aligned = (uintptr_t)a.dst % 4 == 0 && a.dst_step % 4 == 0;
+    OPK_CHECK_ARG(a.dst && a.n > 0 && a.w > 0 && a.h > 0, "empty output image");
+    OPK_CHECK_ARG(a.dst_step >= (size_t)a.w * 3, "row step shorter than the row");
+    OPK_CHECK_ARG(a.cast == 0 || a.cast == 1, "unknown cast");
+    OPK_CHECK_ARG(a.nlayers >= 0 && a.nlayers <= kRenderMaxLayers, "too many layers");
+    for (int l = 0; l < a.nlayers; ++l)
+        OPK_CHECK_ARG(a.layer[l].offsets && (a.layer[l].total == 0 || a.layer[l].geom),
+                      "NULL layer");
+    check_warp(a.warp, a.w, a.h);
+    const dim3 grid = batch_tiles(a.w, a.h, a.n), block(kTileW * kTileH);
+    if (a.warp.ksize == 0)
+        hipLaunchKernelGGL(render_frames_kernel<0>, grid, block, 0, stream, a);
+    else if (a.warp.ksize == 2)
+        hipLaunchKernelGGL(render_frames_kernel<2>, grid, block, 0, stream, a);
+    else
+        hipLaunchKernelGGL(render_frames_kernel<4>, grid, block, 0, stream, a);
     OPK_LAUNCH_CHECK();
 }
 
