@@ -663,6 +663,61 @@ int opk_pose_render_frames(opk_pose* pose, uint8_t* dst_dev, size_t dst_step, in
                            double scale_input_to_output, float render_threshold, float alpha,
                            int googly_eyes, int blend_original, int cast);
 
+/* The heat layer of opk_render_frames_heat: what one of opk_render_pose_heat_map / _heat_maps /
+ * _paf / _pafs / _distance would draw on each frame, from frame f's own stack of heat_dev. */
+#define OPK_HEAT_NONE 0     /* opk_render_element only: element 0, the keypoints               */
+#define OPK_HEAT_PART 1     /* opk_render_pose_heat_map, channel `channel`                     */
+#define OPK_HEAT_PARTS 2    /* opk_render_pose_heat_maps of pose_model                         */
+#define OPK_HEAT_PAF 3      /* opk_render_pose_paf, channels `channel`, `channel` + 1          */
+#define OPK_HEAT_PAFS 4     /* opk_render_pose_pafs of pose_model                              */
+#define OPK_HEAT_DISTANCE 5 /* opk_render_pose_distance, channel `channel`                     */
+typedef struct opk_render_heat {
+    int kind;               /* OPK_HEAT_PART, OPK_HEAT_PARTS, OPK_HEAT_PAF, OPK_HEAT_PAFS, OPK_HEAT_DISTANCE */
+    int pose_model;
+    int channel;            /* PART / DISTANCE: the channel; PAF: its first channel */
+    const float* heat_dev;  /* [n][channels][heat_h][heat_w] */
+    int channels, heat_w, heat_h;
+    float scale_to_keep_ratio, alpha;
+} opk_render_heat;
+
+/* opk_render_frames_heat: opk_render_frames with a heat layer drawn after the warp and before the
+ *   0..3 keypoint layers -- every element op::PoseGpuRenderer::renderPose can draw
+ *   (src/openpose/pose/poseGpuRenderer.cpp:102-202, --part_to_show) for a batch, in the same one
+ *   pass per pixel.  The result bytes are exactly those of opk_cvmat_to_output -> the matching
+ *   opk_render_pose_* heat call per frame -> opk_render_*_keypoints per frame and layer (blending
+ *   on) -> opk_output_to_cvmat.  A tile's heat samples are evaluated once into LDS where their
+ *   window fits it and per pixel where it does not; the bytes are the same.
+ *   Errors before any device work, OPK_ERR_ARG: "Alpha must be in the range [0, 1].", "Invalid
+ *   Model." (PARTS, PAF, PAFS), an unknown kind, a channel outside the stack, an empty heat map,
+ *   heat_dev NULL with n > 0, and blend_original == 0 (the heat renders never clear the frame: the
+ *   reference expresses "no blending" as alpha 1).  heat NULL: opk_render_frames.
+ * opk_render_element: host-only; the heat kind and channel of renderPose's elementRendered for a
+ *   model of P parts, background flag b, PB = P + b and N pairs: 0 the keypoints (OPK_HEAT_NONE);
+ *   1 channel P if b else 0; 2 all parts; 3 all PAFs; 4 .. PB+2 part e - 3 - b; PB+3 .. PB+2+N the
+ *   PAF whose first channel is PB + map_idx[2 (e - PB - 3)]; above that, for BODY_25D only (else
+ *   "Neck-part distance channel only for BODY_25D."), its 2 (P - 1) distance channels
+ *   PB + 2N + (e - (PB+2+N) - 1).  An element below 0 or past the model's last
+ *   (getNumberElementsToRender, poseParametersRender.cpp:98-113) is OPK_ERR_ARG.
+ * opk_pose_render_frames_element: element 0 is opk_pose_render_frames (alpha_keypoint); any other
+ *   element of the pipeline's model is drawn as the heat layer, without keypoints, straight from
+ *   the collected batch's net output (the lazy resize/merge of the pipeline, CPU or CUDA map
+ *   semantics, 1..N scales): the full-resolution stack is neither written nor read.  Scale
+ *   scale_net_to_output * scale_input_to_output, alpha blend_original ? alpha_heatmap : 1, as
+ *   renderPose.  OPK_ERR_STATE when nothing is collected, n is not the batch's frame count, or a
+ *   later batch is in flight (its net forward overwrites the net output). */
+int opk_render_frames_heat(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, int out_w, int out_h,
+                           const uint8_t* frames_dev, int n, int width, int height, size_t step,
+                           double scale_input_to_output, const opk_render_layer* layers,
+                           int n_layers, int blend_original, int cast,
+                           const opk_render_heat* heat);
+int opk_render_element(int pose_model, int element, int* kind, int* channel);
+int opk_pose_render_frames_element(opk_pose* pose, uint8_t* dst_dev, size_t dst_step, int out_w,
+                                   int out_h, const uint8_t* frames_dev, int n, int width,
+                                   int height, size_t step, double scale_input_to_output,
+                                   int element, float render_threshold, float alpha_keypoint,
+                                   float alpha_heatmap, int googly_eyes, int blend_original,
+                                   int cast);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,7 +131,19 @@ _SIGS = {
                                _i, _i]),
     "opk_pose_render_frames": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _i, _i, _i, _c.c_size_t, _d,
                                     _f, _f, _i, _i, _i]),
+    "opk_render_frames_heat": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _i, _i, _i, _c.c_size_t, _d, _p,
+                                    _i, _i, _i, _p]),
+    "opk_render_element": (_i, [_i, _i, _ip, _ip]),
+    "opk_pose_render_frames_element": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _i, _i, _i,
+                                            _c.c_size_t, _d, _i, _f, _f, _f, _i, _i, _i]),
 }
+
+
+class RenderHeatStruct(ctypes.Structure):
+    """opk_render_heat (include/opk.h)."""
+    _fields_ = [("kind", _i), ("pose_model", _i), ("channel", _i), ("heat_dev", _p),
+                ("channels", _i), ("heat_w", _i), ("heat_h", _i), ("scale_to_keep_ratio", _f),
+                ("alpha", _f)]
 
 
 class RenderLayerStruct(ctypes.Structure):

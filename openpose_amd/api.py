@@ -38,6 +38,29 @@ class RenderLayer:
         self.alpha, self.pose_model, self.googly_eyes = alpha, pose_model, googly_eyes
 
 
+# opk_render_heat.kind (OPK_HEAT_*); HEAT_NONE is render_element's answer for the keypoints
+HEAT_NONE, HEAT_PART, HEAT_PARTS, HEAT_PAF, HEAT_PAFS, HEAT_DISTANCE = 0, 1, 2, 3, 4, 5
+
+
+class RenderHeat:
+    """The heat layer of Context.render_frames: what render_heat_map (HEAT_PART; HEAT_DISTANCE),
+    render_heat_maps (HEAT_PARTS) or render_pafs (HEAT_PAF: channel = its x channel; HEAT_PAFS)
+    draws on each frame from heat float32 CUDA [n, channels, hh, hw], frame pixel x sampling
+    (x + 0.5) / scale - 0.5."""
+
+    def __init__(self, kind, heat, scale, channel=0, alpha=0.7, pose_model=BODY_25):
+        self.kind, self.heat, self.scale, self.channel = kind, heat, scale, channel
+        self.alpha, self.pose_model = alpha, pose_model
+
+
+def render_element(pose_model, element):
+    """(HEAT_* kind, channel) of op::PoseGpuRenderer::renderPose's element (--part_to_show)."""
+    kind, channel = ctypes.c_int(0), ctypes.c_int(0)
+    check(_lib.load().opk_render_element(pose_model, element, ctypes.byref(kind),
+                                         ctypes.byref(channel)))
+    return kind.value, channel.value
+
+
 def _row_bytes(t, n, h, w):
     """dst_step of a uint8 image batch: [n, h, w, 3], or [n, h, row bytes] with padded rows."""
     assert t.dtype == torch.uint8 and t.is_contiguous() and t.shape[0] == n and t.shape[1] == h
@@ -245,10 +268,11 @@ class Context:
         return out
 
     def render_frames(self, frames, layers, scale=1.0, out_size=None, blend_original=True,
-                      cast=CAST_CPU, out=None):
-        """CvMatToOpOutput -> the keypoint layers in order -> OpOutputToCvMat in one kernel:
-        frames [n, h, w, 3] uint8 BGR (CUDA), layers a list of RenderLayer -> uint8
-        [n, out_h, out_w, 3] (or into the rows of `out`, uint8 [n, out_h, row bytes])."""
+                      cast=CAST_CPU, out=None, heat=None):
+        """CvMatToOpOutput -> the heat layer (a RenderHeat), if any -> the keypoint layers in
+        order -> OpOutputToCvMat in one kernel: frames [n, h, w, 3] uint8 BGR (CUDA), layers a
+        list of RenderLayer -> uint8 [n, out_h, out_w, 3] (or into the rows of `out`, uint8
+        [n, out_h, row bytes])."""
         n, h, w, c = frames.shape
         assert c == 3 and frames.dtype == torch.uint8
         ow, oh = out_size if out_size is not None else (w, h)
@@ -273,9 +297,23 @@ class Context:
             s.keypoints_dev = None if l.keypoints is None else _ptr(l.keypoints)
             s.counts_host = counts
             s.render_threshold, s.alpha, s.googly_eyes = l.threshold, l.alpha, int(l.googly_eyes)
-        check(self.L.opk_render_frames(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh,
-                                       _ptr(frames), n, w, h, w * 3, float(scale), arr, len(layers),
-                                       int(blend_original), cast))
+        if heat is None:
+            check(self.L.opk_render_frames(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh,
+                                           _ptr(frames), n, w, h, w * 3, float(scale), arr,
+                                           len(layers), int(blend_original), cast))
+            return out
+        hs = _lib.RenderHeatStruct()
+        hs.kind, hs.pose_model, hs.channel = heat.kind, heat.pose_model, heat.channel
+        if heat.heat is not None:
+            assert heat.heat.dtype == torch.float32 and heat.heat.dim() == 4
+            assert heat.heat.shape[0] == n, "one heat stack per frame"
+            hs.heat_dev = _ptr(heat.heat)
+            hs.channels, hs.heat_h, hs.heat_w = heat.heat.shape[1:]
+        hs.scale_to_keep_ratio, hs.alpha = heat.scale, heat.alpha
+        check(self.L.opk_render_frames_heat(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh,
+                                            _ptr(frames), n, w, h, w * 3, float(scale), arr,
+                                            len(layers), int(blend_original), cast,
+                                            ctypes.byref(hs)))
         return out
 
     def paf_scores(self, scores, heat, peaks, pose_model=BODY_25, inter_th=CONNECT_INTER_THRESHOLD,
@@ -743,17 +781,22 @@ class PoseExtractor:
         return kp[:n], ks[:n]
 
     def render_frames(self, frames, scale=1.0, out_size=None, threshold=0.05, alpha=0.6,
-                      googly_eyes=False, blend_original=True, cast=CAST_CPU, out=None):
+                      googly_eyes=False, blend_original=True, cast=CAST_CPU, out=None, element=0,
+                      alpha_heatmap=0.7):
         """The last collected batch drawn on its frames [n, h, w, 3] uint8 BGR (CUDA) ->
-        uint8 [n, out_h, out_w, 3]; keypoints are scaled by `scale` (scaleInputToOutput)."""
+        uint8 [n, out_h, out_w, 3]; keypoints are scaled by `scale` (scaleInputToOutput).
+        element (--part_to_show, see render_element): 0 the keypoints; any other draws that heat
+        map / PAF of the batch instead, evaluated from the net output (no full-resolution stack
+        is written), blended with alpha_heatmap."""
         n, h, w, c = frames.shape
         assert c == 3 and frames.dtype == torch.uint8
         ow, oh = out_size if out_size is not None else (w, h)
         if out is None:
             out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
-        check(self.L.opk_pose_render_frames(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh,
-                                            _ptr(frames), n, w, h, w * 3, float(scale), threshold,
-                                            alpha, int(googly_eyes), int(blend_original), cast))
+        check(self.L.opk_pose_render_frames_element(
+            self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh, _ptr(frames), n, w, h, w * 3,
+            float(scale), int(element), threshold, alpha, alpha_heatmap, int(googly_eyes),
+            int(blend_original), cast))
         return out
 
     def set_timing(self, on=True):

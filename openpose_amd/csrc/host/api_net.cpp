@@ -547,6 +547,37 @@ int opk_pose_render_frames(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w
     });
 }
 
+int opk_pose_render_frames_element(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w,
+                                   int out_h, const uint8_t* frames, int n, int width, int height,
+                                   size_t step, double scale, int element, float threshold,
+                                   float alpha_keypoint, float alpha_heatmap, int googly_eyes,
+                                   int blend_original, int cast)
+{
+    if (element == 0)
+        return opk_pose_render_frames(p, dst, dst_step, out_w, out_h, frames, n, width, height,
+                                      step, scale, threshold, alpha_keypoint, googly_eyes,
+                                      blend_original, cast);
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        const opk::PoseHip& pose = *p->pose;
+        opk_render_heat heat{};
+        heat.pose_model = pose.model();
+        opk::render_element(pose.model(), element, &heat.kind, &heat.channel);
+        if (pose.frames() == 0) throw opk::Error(OPK_ERR_STATE, "no collected batch to render");
+        if (n != pose.frames())
+            throw opk::Error(OPK_ERR_STATE, "the collected batch has " +
+                                                std::to_string(pose.frames()) + " frames, not " +
+                                                std::to_string(n));
+        const opk::HeatMap& lazy = pose.lazy_heat();
+        // renderPose: scaleNetToOutput * scaleInputToOutput, both float; "no blending" is alpha 1,
+        // so the frame is never cleared
+        heat.scale_to_keep_ratio = pose.scale_net_to_output() * (float)scale;
+        heat.alpha = blend_original ? alpha_heatmap : 1.f;
+        opk::render_frames(p->ctx, dst, dst_step, out_w, out_h, frames, n, width, height, step,
+                           scale, nullptr, 0, 1, cast, nullptr, 0, &heat, &lazy);
+    });
+}
+
 int opk_pose_net_input(opk_pose* p, int scale, const float** input_dev, int* net_w, int* net_h)
 {
     return guarded_net([&] {

@@ -121,6 +121,14 @@ void PoseHip::heatmap_size(int shape[4]) const
     shape[0] = n_; shape[1] = slots_[last_].heat.channels; shape[2] = hh_; shape[3] = hw_;
 }
 
+const HeatMap& PoseHip::lazy_heat() const
+{
+    if (last_ < 0) throw Error(3, "no collected batch");
+    if (count_ != 0)
+        throw Error(3, "heat maps are kept only while no later batch is in flight");
+    return slots_[last_].heat;
+}
+
 float* PoseHip::heatmaps(int shape[4])
 {
     OPK_CHECK_ARG(last_ >= 0, "no collected batch");

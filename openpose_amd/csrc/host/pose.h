@@ -68,6 +68,9 @@ public:
     // later batch is in flight (its net forward overwrites the net output)
     float* heatmaps(int shape[4]);
     void heatmap_size(int shape[4]) const;   // the last collected batch's, nothing materialised
+    // the last collected batch's lazy map itself (the batch render's heat layer reads it); an
+    // OPK_ERR_STATE error under heatmaps()' conditions; nothing is materialised
+    const HeatMap& lazy_heat() const;
     float* peaks(int shape[4]) const;
     // PoseExtractorNet::getHeatMapsCopy (poseExtractorNet.cpp:106-244) for every frame of the last
     // collected batch: types bit 0 parts, bit 1 background, bit 2 PAFs (in that order), scale_mode

@@ -211,12 +211,93 @@ LayerRender layer_render(const opk_render_layer& l)
             l.googly_eyes ? pr.eye2 : -1, 127, 100.f, 120.f};
 }
 
+// the heat layer's checks (the per-frame heat renders' own, and the stack's bounds) and everything
+// of it that needs no device: the kind's channels and the map
+RenderFramesHeat heat_layer(const opk_render_heat& h, int n, int blend_original, const HeatMap* lazy)
+{
+    RenderFramesHeat H{};
+    OPK_CHECK_ARG(h.kind >= OPK_HEAT_PART && h.kind <= OPK_HEAT_DISTANCE, "unknown heat kind");
+    check_alpha(h.alpha);
+    const bool model = h.kind == OPK_HEAT_PARTS || h.kind == OPK_HEAT_PAF || h.kind == OPK_HEAT_PAFS;
+    OPK_CHECK_ARG(!model || (h.pose_model >= 0 && h.pose_model < kPoseModels), "Invalid Model.");
+    OPK_CHECK_ARG(blend_original != 0,
+                  "the heat renders never clear the frame: no blending is alpha 1");
+    const int channels = lazy ? lazy->channels : h.channels;
+    const int hw = lazy ? lazy->w : h.heat_w, hh = lazy ? lazy->h : h.heat_h;
+    OPK_CHECK_ARG(hw > 0 && hh > 0 && channels > 0, "empty heat map");
+    static_assert(OPK_HEAT_PART == kHeatPart && OPK_HEAT_PARTS == kHeatParts &&
+                      OPK_HEAT_PAF == kHeatPaf && OPK_HEAT_PAFS == kHeatPafs &&
+                      OPK_HEAT_DISTANCE == kHeatDistance && OPK_HEAT_NONE == kHeatNone,
+                  "OPK_HEAT_* are RenderHeatKind's values");
+    H.kind = h.kind;
+    H.channel = h.channel;
+    H.count = 1;
+    int used = 1;
+    if (h.kind == OPK_HEAT_PARTS) {
+        H.channel = 0;
+        H.count = used = pose_model(h.pose_model).parts;
+    } else if (h.kind == OPK_HEAT_PAF) {
+        used = 2;
+    } else if (h.kind == OPK_HEAT_PAFS) {
+        // renderPosePAFsGpu (renderPose.cu:818-834): every pair, from the first PAF channel
+        const auto& m = pose_model(h.pose_model);
+        H.channel = m.parts + (m.bkg ? 1 : 0);
+        H.count = m.npairs();
+        used = 2 * H.count;
+    }
+    OPK_CHECK_ARG(H.channel >= 0 && H.channel <= channels - used, "channel outside the heat stack");
+    H.scale = h.scale_to_keep_ratio;
+    H.alpha = h.alpha;
+    if (lazy) {
+        H.map = *lazy;
+    } else {
+        OPK_CHECK_ARG(n == 0 || h.heat_dev, "NULL heat maps");
+        H.map = heat_materialised(h.heat_dev, channels, hh, hw);
+    }
+    return H;
+}
+
 }  // namespace
+
+void render_element(int model, int element, int* kind, int* channel)
+{
+    OPK_CHECK_ARG(model >= 0 && model < kPoseModels, "Invalid Model.");
+    const auto& m = pose_model(model);
+    // PoseGpuRenderer::renderPose (poseGpuRenderer.cpp:102-202)
+    const int parts = m.parts, bkg = m.bkg ? 1 : 0, pb = parts + bkg, pairs = m.npairs();
+    const int last_paf = pb + 2 + pairs;
+    OPK_CHECK_ARG(element >= 0, "negative element");
+    int k = OPK_HEAT_NONE, c = 0;
+    if (element == 0) {
+    } else if (element == 2) {
+        k = OPK_HEAT_PARTS;
+    } else if (element == 3) {
+        k = OPK_HEAT_PAFS;
+        c = pb;
+    } else if (element <= pb + 2) {
+        k = OPK_HEAT_PART;
+        c = element == 1 ? (bkg ? parts : 0) : element - 3 - bkg;
+    } else if (element <= last_paf) {
+        k = OPK_HEAT_PAF;
+        c = pb + m.map_idx.at((size_t)(element - pb - 3) * 2);
+    } else {
+        OPK_CHECK_ARG(model == 9, "Neck-part distance channel only for BODY_25D.");
+        // getNumberElementsToRender (poseParametersRender.cpp:98-113): 2 (parts - 1) of them
+        OPK_CHECK_ARG(element <= last_paf + 2 * (parts - 1),
+                      "element past the model's last (" +
+                          std::to_string(last_paf + 2 * (parts - 1)) + ")");
+        k = OPK_HEAT_DISTANCE;
+        c = pb + 2 * pairs + (element - last_paf - 1);
+    }
+    if (kind) *kind = k;
+    if (channel) *channel = c;
+}
 
 void render_frames(Context* ctx, uint8_t* dst, size_t dst_step, int out_w, int out_h,
                    const uint8_t* frames, int n, int width, int height, size_t step, double scale,
                    const opk_render_layer* layers, int n_layers, int blend_original, int cast,
-                   const float* kp_host, size_t kp_floats)
+                   const float* kp_host, size_t kp_floats, const opk_render_heat* heat,
+                   const HeatMap* lazy)
 {
     // everything that does not depend on the frames first, then each frame's counts; device work
     // starts only after the last check
@@ -228,6 +309,8 @@ void render_frames(Context* ctx, uint8_t* dst, size_t dst_step, int out_w, int o
     OPK_CHECK_ARG(dst_step == 0 || dst_step >= (size_t)out_w * 3, "row step shorter than the row");
     LayerRender lr[kRenderMaxLayers];
     for (int l = 0; l < n_layers; ++l) lr[l] = layer_render(layers[l]);
+    RenderFramesHeat heat_args{};
+    if (heat) heat_args = heat_layer(*heat, n, blend_original, lazy);
     if (n == 0) return;
     OPK_CHECK_ARG(dst && frames, "NULL buffer");
     // prefix offsets of every layer: [n_layers][n + 1]
@@ -268,6 +351,12 @@ void render_frames(Context* ctx, uint8_t* dst, size_t dst_step, int out_w, int o
     a.blend = blend_original ? 1 : 0;
     a.cast = cast;
     a.nlayers = n_layers;
+    a.heat = heat_args;
+    if (heat && heat->kind == OPK_HEAT_PARTS) {
+        const auto& coco = ctx->render_table(kRtCoco);   // COCO_COLORS (renderPose.cu:427)
+        a.heat.colors = coco.colors;
+        a.heat.ncolors = coco.ncolors;
+    }
     if (n_layers > 0) {
         int* dev = static_cast<int*>(ctx->frames_offsets.get(offsets.size() * sizeof(int)));
         if (offsets != ctx->frames_offsets_host) {
@@ -485,6 +574,24 @@ int opk_render_frames(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, int out_w
         opk::render_frames(ctx, dst_dev, dst_step, out_w, out_h, frames_dev, n, width, height,
                            step, scale_input_to_output, layers, n_layers, blend_original, cast);
     });
+}
+
+int opk_render_frames_heat(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, int out_w, int out_h,
+                           const uint8_t* frames_dev, int n, int width, int height, size_t step,
+                           double scale_input_to_output, const opk_render_layer* layers,
+                           int n_layers, int blend_original, int cast, const opk_render_heat* heat)
+{
+    return opk::guarded_render([&] {
+        OPK_CHECK_ARG(ctx != nullptr, "NULL argument");
+        opk::render_frames(ctx, dst_dev, dst_step, out_w, out_h, frames_dev, n, width, height,
+                           step, scale_input_to_output, layers, n_layers, blend_original, cast,
+                           nullptr, 0, heat);
+    });
+}
+
+int opk_render_element(int pose_model, int element, int* kind, int* channel)
+{
+    return opk::guarded_render([&] { opk::render_element(pose_model, element, kind, channel); });
 }
 
 }  // extern "C"

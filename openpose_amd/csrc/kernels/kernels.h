@@ -155,6 +155,22 @@ struct RenderFramesLayer {
     float alpha;
 };
 constexpr int kRenderMaxLayers = 3;
+// The heat layer of the fused render: what one of the heat-map renders below draws on each frame,
+// before the keypoint layers.  `map` is the stack [n][channels][hh][hw] (map.h = hh, map.w = hw),
+// materialised (map.heat) or lazy: every value is heat_at(map, f * channels + c, x, y).
+enum RenderHeatKind { kHeatNone = 0, kHeatPart, kHeatParts, kHeatPaf, kHeatPafs, kHeatDistance };
+struct RenderFramesHeat {
+    int kind;
+    int channel;           // Part / Distance: the channel; Paf / Pafs: the first x channel
+    int count;             // Parts: the parts; Paf: 1; Pafs: the pairs
+    float scale, alpha;    // target pixel x samples (x + 0.5) / scale - 0.5
+    const float* colors;   // Parts: the RGB table and its rows
+    int ncolors;
+    int staged;            // set by the launcher: the tile's heat window of this kind fits the LDS
+    HeatMap map;
+};
+// floats of the LDS window a tile's heat values are staged in (the kernel's `items` array)
+constexpr int kRenderHeatWindow = 4096;
 struct RenderFramesArgs {
     uint8_t* dst;
     size_t dst_step;
@@ -163,9 +179,13 @@ struct RenderFramesArgs {
     int blend, cast, nlayers;
     int dst_aligned;   // set by the launcher: dst and dst_step are multiples of 4
     RenderFramesLayer layer[kRenderMaxLayers];
+    RenderFramesHeat heat;   // kind kHeatNone: no heat layer
 };
-// warp -> every layer in order -> cast, one pass per pixel
+// warp -> the heat layer -> every layer in order -> cast, one pass per pixel
 void launch_render_frames(const RenderFramesArgs& a, hipStream_t stream);
+// whether launch_render_frames stages a tile's heat window of `kind` at `scale` in LDS (else every
+// pixel evaluates its own samples)
+bool render_heat_staged(int kind, float scale);
 // heat-map renders: frame [h][w][3] BGR; heat [channels][hh][hw]; target pixel x samples the heat
 // map at (x + 0.5) / scale - 0.5
 struct RenderHeatArgs {

@@ -22,7 +22,8 @@
 //
 // Heat maps: renderBodyPartHeatMap (bicubic + getColorHeatMap), renderBodyPartHeatMaps (nearest,
 // COCO colors) and renderPartAffinities (getColorXYAffinity) of renderPose.cu:44-119,419-527,
-// one pixel per lane.
+// one pixel per lane; the same arithmetic is the heat layer of the fused batch render
+// (render_frames_kernel), there on heat values staged per tile in LDS or evaluated lazily.
 //
 // Arithmetic is the reference's expression by expression with every mul / add rounded separately
 // (the library builds with -ffp-contract=off); atan2f / sinf / cosf are the device library's, so
@@ -32,6 +33,8 @@
 #include "heat_dev.h"
 #include "warp_dev.h"
 #include "../common.h"
+
+#include <cmath>
 
 namespace opk {
 
@@ -433,65 +436,6 @@ __global__ __launch_bounds__(256) void output_to_cvmat_kernel(uint8_t* __restric
     }
 }
 
-template <int K>
-__global__ __launch_bounds__(256) void render_frames_kernel(RenderFramesArgs a)
-{
-    __shared__ unsigned short plist[kRenderMaxPeople];
-    __shared__ float4 items[256][4];
-    __shared__ int wcount[4];
-    const int f = blockIdx.z;
-    const RenderTile t = render_tile(a.w, a.h);
-    // 1. the pixel of the output image, in registers from here to the store
-    float b = 0.f, g = 0.f, r = 0.f;
-    if (t.inside && a.blend) {
-        int u[3];
-        output_pixel<K>(u, a.warp, f, t.x, t.y);
-        b = (float)u[0];
-        g = (float)u[1];
-        r = (float)u[2];
-    }
-    // 2. every layer in order on the frame's own people
-    for (int l = 0; l < a.nlayers; ++l) {
-        const RenderFramesLayer& L = a.layer[l];
-        const int first = L.offsets[f], people = L.offsets[f + 1] - first;
-        render_view_pixel(render_view(L.geom, L.total, first, people, L.npairs, L.parts, L.colors,
-                                      L.alpha),
-                          t, plist, items, wcount, b, g, r);
-    }
-    // 3. OpOutputToCvMat's cast
-    const unsigned cb = cast_u8(b, a.cast), cg = cast_u8(g, a.cast), cr = cast_u8(r, a.cast);
-    if (!a.dst_aligned) {
-        if (t.inside) {
-            uint8_t* d = a.dst + ((size_t)f * a.h + t.y) * a.dst_step + (size_t)t.x * 3;
-            d[0] = (uint8_t)cb;
-            d[1] = (uint8_t)cg;
-            d[2] = (uint8_t)cr;
-        }
-        return;
-    }
-    // rows on 4-byte boundaries (a tile starts at byte 96 * blockIdx.x of its rows): the tile's
-    // 8 x 96 bytes go through LDS -- `items` is idle, every use of it ended at a barrier -- and
-    // leave as 4-byte stores, 24 lanes a row; a row's last 1..3 bytes, if any, as bytes
-    uint8_t* stage = reinterpret_cast<uint8_t*>(items);
-    uint8_t* mine = stage + threadIdx.x * 3;   // (threadIdx.x / 32) * 96 + (threadIdx.x % 32) * 3
-    mine[0] = (uint8_t)cb;
-    mine[1] = (uint8_t)cg;
-    mine[2] = (uint8_t)cr;
-    __syncthreads();
-    const int tx0 = blockIdx.x * kTileW, ty0 = blockIdx.y * kTileH;
-    const int rows = min(kTileH, a.h - ty0), row_bytes = min(kTileW, a.w - tx0) * 3;
-    const int row = threadIdx.x / 24, o = (threadIdx.x % 24) * 4;
-    if (row < rows && o < row_bytes) {   // row < 8 only for threadIdx.x < 192
-        uint8_t* d = a.dst + ((size_t)f * a.h + ty0 + row) * a.dst_step + (size_t)tx0 * 3 + o;
-        const uint8_t* s = stage + row * (kTileW * 3) + o;
-        if (o + 4 <= row_bytes) {
-            *reinterpret_cast<unsigned*>(d) = *reinterpret_cast<const unsigned*>(s);
-        } else {
-            for (int i = 0; i < row_bytes - o; ++i) d[i] = s[i];
-        }
-    }
-}
-
 // getColorHeatMap (renderPose.cu:44-80) with vmin 0, vmax 1
 __device__ __forceinline__ void color_heat(float* c, float v)
 {
@@ -556,21 +500,134 @@ __device__ __forceinline__ void blend_bgr(float* px, const float* c, float alpha
     px[0] = (1.f - alpha) * px[0] + alpha * c[2];
 }
 
-// renderBodyPartHeatMap (renderPose.cu:454-480): one channel, bicubic, getColorHeatMap
+// ---- the per-pixel arithmetic of the heat-map renders, shared by the per-frame kernels (which read
+//      a materialised stack) and by the heat layer of render_frames_kernel (a staged window or a
+//      lazy map).  A pixel first gathers its taps -- sample k of a HeatSampler around a base
+//      (channel, x, y) --, then the functions below combine the gathered values.
+
+// the heat-map coordinate a target pixel samples
+__device__ __forceinline__ float heat_source(int x, float scale)
+{
+    return ((float)x + 0.5f) / scale - 0.5f;
+}
+
+// Tap k = 0 .. n-1 of a pixel: channel ch + (k >> cshift), column clamp(x + (k & xmask)), row
+// clamp(y + ((k >> yshift) & ymask)), clamped into the map
+struct HeatSampler {
+    int n, cshift, xmask, yshift, ymask;
+};
+// cubicSequentialData's 4x4 taps (cuda.hu:92-109) from base (x1 - 1, y1 - 1): columns max(0, x1 - 1),
+// x1, min(w - 1, x1 + 1), min(w - 1, min(w - 1, x1 + 1) + 1) are clamp(x1 - 1 + i) for x1 in the map
+constexpr HeatSampler kSampleBicubic{16, 4, 3, 2, 3};
+// one PAF bilinear: channel x then y, each (x1, y1), (x2, y1), (x1, y2), (x2, y2)
+constexpr HeatSampler kSamplePaf{8, 2, 1, 1, 1};
+// one PAF at its base pixel: channel x, channel y
+constexpr HeatSampler kSamplePafBase{2, 0, 0, 0, 0};
+constexpr HeatSampler kSampleOne{1, 0, 0, 0, 0};
+constexpr int kHeatMaxTaps = 16;
+
+struct HeatTap {
+    int ch, x, y;
+};
+__device__ __forceinline__ HeatTap heat_tap(const HeatSampler& S, int k, int ch, int x, int y, int hw,
+                                            int hh)
+{
+    return HeatTap{ch + (k >> S.cshift), heat_clampi(x + (k & S.xmask), 0, hw - 1),
+                   heat_clampi(y + ((k >> S.yshift) & S.ymask), 0, hh - 1)};
+}
+// every tap from a materialised stack [channels][area]
+__device__ __forceinline__ void heat_gather_stack(float* v, const HeatSampler& S,
+                                                  const float* __restrict__ heat, size_t area, int ch,
+                                                  int x, int y, int hw, int hh)
+{
+#pragma unroll
+    for (int k = 0; k < kHeatMaxTaps; ++k)
+        if (k < S.n) {
+            const HeatTap t = heat_tap(S, k, ch, x, y, hw, hh);
+            v[k] = heat[t.ch * area + (size_t)t.y * hw + t.x];
+        }
+}
+
+// the base pixel and fractions of cubicSequentialData (bicubic and PAF samples)
+struct HeatBase {
+    int x1, y1;
+    float dx, dy;
+};
+__device__ __forceinline__ HeatBase heat_base(float xs, float ys, int hw, int hh)
+{
+    HeatBase b;
+    b.x1 = heat_clampi((int)floorf(xs), 0, hw - 1);
+    b.dx = xs - (float)b.x1;
+    b.y1 = heat_clampi((int)floorf(ys), 0, hh - 1);
+    b.dy = ys - (float)b.y1;
+    return b;
+}
+
+// renderBodyPartHeatMap (renderPose.cu:454-480): bicubicInterpolate (cuda.hu:125-145) of
+// kSampleBicubic's values
+__device__ __forceinline__ float heat_bicubic(const float* v, float dx, float dy)
+{
+    float t[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) t[i] = cuda_cubic(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3], dx);
+    return cuda_cubic(t[0], t[1], t[2], t[3], dy);
+}
+
+// renderBodyPartHeatMaps (renderPose.cu:419-452): the nearest sample's offset y * hw + x inside a
+// plane.  int(xSource + 1e-5) is a double add, truncated into [0, width] (not width - 1), so the
+// offset can pass the end of its row or plane by up to width + 1 values.
+__device__ __forceinline__ size_t heat_maps_offset(float xs, float ys, int hw, int hh)
+{
+    int xh = (int)((double)xs + 1e-5), yh = (int)((double)ys + 1e-5);
+    xh = xh > hw ? hw : (xh < 0 ? 0 : xh);
+    yh = yh > hh ? hh : (yh < 0 ? 0 : yh);
+    return (size_t)yh * hw + xh;
+}
+// one part's contribution: saturated value times the part's color
+__device__ __forceinline__ void heat_maps_add(float* c, float h, const float* col)
+{
+    const float v = fminf(fmaxf(h, 0.f), 1.f);   // __saturatef (NaN -> 0)
+    c[0] += v * col[0];
+    c[1] += v * col[1];
+    c[2] += v * col[2];
+}
+
+// renderPartAffinities (renderPose.cu:482-527): one PAF's color added to c; X / Y its gathered
+// values: kSamplePaf's four each (bilinear) or the base pixel's
+__device__ __forceinline__ void paf_add(float* c, const float* X, const float* Y, float dx, float dy,
+                                        bool bilinear)
+{
+    float vx = X[0], vy = Y[0];
+    if (bilinear) {
+        const float xB = X[1], xC = X[2], xD = X[3];
+        vx = (1 - dx) * (1 - dy) * vx + dx * (1 - dy) * xB + (1 - dx) * dy * xC + dx * dy * xD;
+        const float yB = Y[1], yC = Y[2], yD = Y[3];
+        vy = (1 - dx) * (1 - dy) * vy + dx * (1 - dy) * yB + (1 - dx) * dy * yC + dx * dy * yD;
+    }
+    float c2[3];
+    color_xy_affinity(c2, vx, vy);
+    c[0] += c2[0];
+    c[1] += c2[1];
+    c[2] += c2[2];
+}
+
+// renderBodyPartHeatMap: one channel, bicubic, getColorHeatMap
 __global__ __launch_bounds__(256) void render_heat_map_kernel(RenderHeatArgs a, int part, int absv)
 {
     const int x = blockIdx.x * kTileW + (threadIdx.x & (kTileW - 1));
     const int y = blockIdx.y * kTileH + threadIdx.x / kTileW;
     if (x >= a.w || y >= a.h) return;
-    const float xs = ((float)x + 0.5f) / a.scale - 0.5f;
-    const float ys = ((float)y + 0.5f) / a.scale - 0.5f;
-    const float v = cuda_bicubic(a.heat + (size_t)part * a.hw * a.hh, xs, ys, a.hw, a.hh);
+    const HeatBase hb = heat_base(heat_source(x, a.scale), heat_source(y, a.scale), a.hw, a.hh);
+    float taps[kHeatMaxTaps];
+    heat_gather_stack(taps, kSampleBicubic, a.heat, (size_t)a.hw * a.hh, part, hb.x1 - 1, hb.y1 - 1,
+                      a.hw, a.hh);
+    const float v = heat_bicubic(taps, hb.dx, hb.dy);
     float c[3];
     color_heat(c, absv ? fabsf(v) : v);
     blend_bgr(a.frame + 3 * ((size_t)y * a.w + x), c, a.alpha);
 }
 
-// renderBodyPartHeatMaps (renderPose.cu:419-452): every part, nearest sample, COCO colors
+// renderBodyPartHeatMaps: every part, nearest sample, COCO colors
 __global__ __launch_bounds__(256) void render_heat_maps_kernel(RenderHeatArgs a, int parts,
                                                                const float* __restrict__ colors,
                                                                int ncolors)
@@ -578,66 +635,296 @@ __global__ __launch_bounds__(256) void render_heat_maps_kernel(RenderHeatArgs a,
     const int x = blockIdx.x * kTileW + (threadIdx.x & (kTileW - 1));
     const int y = blockIdx.y * kTileH + threadIdx.x / kTileW;
     if (x >= a.w || y >= a.h) return;
-    const float xs = ((float)x + 0.5f) / a.scale - 0.5f;
-    const float ys = ((float)y + 0.5f) / a.scale - 0.5f;
-    // int(xSource + 1e-5): a double add; truncated into [0, width] (not width - 1)
-    int xh = (int)((double)xs + 1e-5), yh = (int)((double)ys + 1e-5);
-    xh = xh > a.hw ? a.hw : (xh < 0 ? 0 : xh);
-    yh = yh > a.hh ? a.hh : (yh < 0 ? 0 : yh);
+    const size_t off = heat_maps_offset(heat_source(x, a.scale), heat_source(y, a.scale), a.hw,
+                                        a.hh);
     const size_t area = (size_t)a.hw * a.hh;
-    // the reference's index can pass the end of its last plane by up to width + 1 values (x or y
-    // truncated to the size itself); those reads are clamped to the stack's last value
+    // reads past the end of the last plane are clamped to the stack's last value
     const size_t last = area * parts - 1;
     float c[3] = {0.f, 0.f, 0.f};
     for (int p = 0; p < parts; ++p) {
-        size_t idx = p * area + (size_t)yh * a.hw + xh;
+        size_t idx = p * area + off;
         idx = idx > last ? last : idx;
-        const float h = a.heat[idx];
-        const float v = fminf(fmaxf(h, 0.f), 1.f);   // __saturatef (NaN -> 0)
-        const float* col = colors + (p % ncolors) * 3;
-        c[0] += v * col[0];
-        c[1] += v * col[1];
-        c[2] += v * col[2];
+        heat_maps_add(c, a.heat[idx], colors + (p % ncolors) * 3);
     }
     blend_bgr(a.frame + 3 * ((size_t)y * a.w + x), c, a.alpha);
 }
 
-// renderPartAffinities (renderPose.cu:482-527): `count` PAFs from channel `first`; one PAF is
-// sampled bilinearly, several at the base pixel of cubicSequentialData
+// renderPartAffinities: `count` PAFs from channel `first`; one PAF is sampled bilinearly, several
+// at the base pixel
 __global__ __launch_bounds__(256) void render_pafs_kernel(RenderHeatArgs a, int first, int count)
 {
     const int x = blockIdx.x * kTileW + (threadIdx.x & (kTileW - 1));
     const int y = blockIdx.y * kTileH + threadIdx.x / kTileW;
     if (x >= a.w || y >= a.h) return;
-    const float xs = ((float)x + 0.5f) / a.scale - 0.5f;
-    const float ys = ((float)y + 0.5f) / a.scale - 0.5f;
-    const int x1 = heat_clampi((int)floorf(xs), 0, a.hw - 1);
-    const int x2 = min(a.hw - 1, x1 + 1);
-    const float dx = xs - (float)x1;
-    const int y1 = heat_clampi((int)floorf(ys), 0, a.hh - 1);
-    const int y2 = min(a.hh - 1, y1 + 1);
-    const float dy = ys - (float)y1;
+    const HeatBase hb = heat_base(heat_source(x, a.scale), heat_source(y, a.scale), a.hw, a.hh);
     const size_t area = (size_t)a.hw * a.hh;
+    const bool bilinear = count == 1;
     float c[3] = {0.f, 0.f, 0.f};
     for (int part = first; part < first + count * 2; part += 2) {
-        const float* X = a.heat + (size_t)part * area;
-        const float* Y = X + area;
-        float vx = X[(size_t)y1 * a.hw + x1], vy = Y[(size_t)y1 * a.hw + x1];
-        if (count == 1) {
-            const float xB = X[(size_t)y1 * a.hw + x2], xC = X[(size_t)y2 * a.hw + x1],
-                        xD = X[(size_t)y2 * a.hw + x2];
-            vx = (1 - dx) * (1 - dy) * vx + dx * (1 - dy) * xB + (1 - dx) * dy * xC + dx * dy * xD;
-            const float yB = Y[(size_t)y1 * a.hw + x2], yC = Y[(size_t)y2 * a.hw + x1],
-                        yD = Y[(size_t)y2 * a.hw + x2];
-            vy = (1 - dx) * (1 - dy) * vy + dx * (1 - dy) * yB + (1 - dx) * dy * yC + dx * dy * yD;
-        }
-        float c2[3];
-        color_xy_affinity(c2, vx, vy);
-        c[0] += c2[0];
-        c[1] += c2[1];
-        c[2] += c2[2];
+        float taps[kHeatMaxTaps];
+        if (bilinear)
+            heat_gather_stack(taps, kSamplePaf, a.heat, area, part, hb.x1, hb.y1, a.hw, a.hh);
+        else
+            heat_gather_stack(taps, kSamplePafBase, a.heat, area, part, hb.x1, hb.y1, a.hw, a.hh);
+        paf_add(c, taps, taps + (bilinear ? 4 : 1), hb.dx, hb.dy, bilinear);
     }
     blend_bgr(a.frame + 3 * ((size_t)y * a.w + x), c, a.alpha);
+}
+
+// ---- the heat layer of the fused render ----------------------------------------------------------
+// A 32x8 tile's pixels sample few heat pixels (about 20x8 per channel at scale 1.95), each of which
+// a lazy map evaluates from 16 net-output taps.  The tile therefore evaluates the window of heat
+// pixels it can touch once, cooperatively, into LDS (`win`, kRenderHeatWindow floats: the `items`
+// array, idle before the keypoint layers), as many channels a pass as fit (all 25 parts of BODY_25
+// at scale 1.95, its 52 PAF channels in two passes); the pixels gather from there.  A tap outside the staged window -- the flat-index overflow of the all-parts
+// render, or every tap when the window does not fit (staged == 0: the heat map is much larger than
+// the output) -- is evaluated directly by the same heat_at, so both routes give the same bits.
+// heat_at is inlined at two places only, the staging loop and the loop over missed taps: each
+// inlined copy reads the by-value kernel argument at some twenty places, and beyond a few hundred
+// such reads the compiler copies the whole argument to scratch instead.
+struct HeatWindow {
+    const float* win;
+    int x0, y0, w, h;    // the staged rectangle of heat pixels (w == 0: nothing staged)
+    int plane0, planes;  // the staged channels
+};
+
+// the rectangle of base pixels clamp(floor(source)) of the tile, grown by lo / hi taps; staged
+// only if `unit` channels of it fit
+__device__ __forceinline__ HeatWindow heat_window(const RenderFramesHeat& H, const float* win, int lo,
+                                                  int hi, int unit)
+{
+    HeatWindow W{win, 0, 0, 0, 0, 0, 0};
+    if (!H.staged) return W;
+    const int tx0 = blockIdx.x * kTileW, ty0 = blockIdx.y * kTileH;
+    // the source coordinate does not decrease with the pixel: the tile's first and last pixel
+    // bound every pixel's base
+    const int bx0 = heat_clampi((int)floorf(heat_source(tx0, H.scale)), 0, H.map.w - 1);
+    const int bx1 = heat_clampi((int)floorf(heat_source(tx0 + kTileW - 1, H.scale)), 0, H.map.w - 1);
+    const int by0 = heat_clampi((int)floorf(heat_source(ty0, H.scale)), 0, H.map.h - 1);
+    const int by1 = heat_clampi((int)floorf(heat_source(ty0 + kTileH - 1, H.scale)), 0, H.map.h - 1);
+    const int x0 = max(0, bx0 - lo), x1 = min(H.map.w - 1, bx1 + hi);
+    const int y0 = max(0, by0 - lo), y1 = min(H.map.h - 1, by1 + hi);
+    const int w = x1 - x0 + 1, h = y1 - y0 + 1;
+    // the launcher's bound holds for every tile; a window that did not fit would stay unstaged
+    if (w <= 0 || h <= 0 || (long long)w * h * unit > kRenderHeatWindow) return W;
+    W.x0 = x0;
+    W.y0 = y0;
+    W.w = w;
+    W.h = h;
+    return W;
+}
+
+// evaluate channels plane0 .. plane0 + planes - 1 of frame f over the window; every thread of the
+// workgroup calls it (barriers inside when staging)
+__device__ __forceinline__ void heat_stage(const RenderFramesHeat& H, HeatWindow& W, float* win, int f,
+                                           int plane0, int planes)
+{
+    W.plane0 = plane0;
+    W.planes = planes;
+    if (!H.staged) return;
+    __syncthreads();   // the previous pass's readers are done
+    const int area = W.w * W.h, total = area * W.planes;
+    for (int i = threadIdx.x; i < total; i += kTileW * kTileH) {
+        const int p = i / area, r = i - p * area;
+        const int y = r / W.w, x = r - y * W.w;
+        win[i] = heat_at(H.map, f * H.map.channels + plane0 + p, W.x0 + x, W.y0 + y);
+    }
+    __syncthreads();
+}
+
+// the taps the staged window holds; returns the mask of those it does not
+__device__ __forceinline__ unsigned heat_gather_window(float* v, const HeatSampler& S,
+                                                       const HeatWindow& W, int ch, int x, int y,
+                                                       int hw, int hh)
+{
+    unsigned miss = 0;
+#pragma unroll
+    for (int k = 0; k < kHeatMaxTaps; ++k)
+        if (k < S.n) {
+            const HeatTap t = heat_tap(S, k, ch, x, y, hw, hh);
+            const unsigned wx = (unsigned)(t.x - W.x0), wy = (unsigned)(t.y - W.y0);
+            const unsigned wp = (unsigned)(t.ch - W.plane0);
+            if (wx < (unsigned)W.w && wy < (unsigned)W.h && wp < (unsigned)W.planes)
+                v[k] = W.win[(wp * W.h + wy) * W.w + wx];
+            else
+                miss |= 1u << k;
+        }
+    return miss;
+}
+// the missed taps of frame f, evaluated
+__device__ __forceinline__ void heat_gather_missed(float* v, unsigned miss, const HeatSampler& S,
+                                                   const RenderFramesHeat& H, int f, int ch, int x,
+                                                   int y)
+{
+#pragma unroll 1
+    for (; miss; miss &= miss - 1) {
+        const int k = __ffs(miss) - 1;
+        const HeatTap t = heat_tap(S, k, ch, x, y, H.map.w, H.map.h);
+        const float h = heat_at(H.map, f * H.map.channels + t.ch, t.x, t.y);
+#pragma unroll
+        for (int j = 0; j < kHeatMaxTaps; ++j) v[j] = j == k ? h : v[j];   // v stays in registers
+    }
+}
+
+// the heat layer's kinds as the kernel is instantiated for them (each instantiation carries its own
+// kind's code and registers only): bicubic part / distance, all parts, one or all PAFs
+constexpr int kHeatModeNone = 0, kHeatModeCubic = 1, kHeatModeParts = 2, kHeatModePaf = 3;
+
+// the heat layer on the thread's pixel (b, g, r) of frame f; every thread of the workgroup calls it
+template <int Mode>
+__device__ __forceinline__ void render_heat_pixel(const RenderFramesHeat& H, const RenderTile& t,
+                                                  int f, float* win, float& b, float& g, float& r)
+{
+    const int hw = H.map.w, hh = H.map.h;
+    const float xs = heat_source(t.x, H.scale), ys = heat_source(t.y, H.scale);
+    constexpr bool cubic = Mode == kHeatModeCubic, parts = Mode == kHeatModeParts;
+    const bool bilinear = !cubic && !parts && H.count == 1;   // renderPartAffinities' one PAF
+    // the channels drawn, from H.channel, in items of one channel or a PAF's two
+    const int unit = cubic || parts ? 1 : 2;
+    const int total = cubic ? 1 : H.count * unit;
+    // what a pass stages: the kind's taps around the tile's bases, as many items as fit
+    HeatWindow W = heat_window(H, win, cubic ? 1 : 0, cubic ? 2 : (parts || bilinear ? 1 : 0), unit);
+    int chunk = total;
+    if (W.w > 0) {
+        chunk = min(total, kRenderHeatWindow / (W.w * W.h));
+        chunk -= chunk % unit;
+    }
+    // the kind's sampler once more, in scalars, for the loop over missed taps
+    const HeatSampler S{cubic ? 16 : (parts ? 1 : (bilinear ? 8 : 2)), cubic ? 4 : (bilinear ? 2 : 0),
+                        cubic ? 3 : (bilinear ? 1 : 0), cubic ? 2 : (bilinear ? 1 : 0),
+                        cubic ? 3 : (bilinear ? 1 : 0)};
+    // the pixel's base: cubicSequentialData's, or the all-parts render's flat index p * area + off
+    // back to (plane p + dq, y, x)
+    const HeatBase hb = heat_base(xs, ys, hw, hh);
+    int bx = cubic ? hb.x1 - 1 : hb.x1, by = cubic ? hb.y1 - 1 : hb.y1, dq = 0;
+    if (parts) {
+        const int off = (int)heat_maps_offset(xs, ys, hw, hh);   // <= area + hw (the launcher's bound)
+        const int area = hw * hh;
+        dq = off / area;
+        const int rem = off - dq * area;
+        by = rem / hw;
+        bx = rem - by * hw;
+    }
+    float c[3] = {0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int c0 = 0; c0 < total; c0 += chunk) {
+        const int staged = min(chunk, total - c0);
+        heat_stage(H, W, win, f, H.channel + c0, staged);
+        if (!t.inside) continue;
+        int color = parts ? c0 % H.ncolors : 0;   // the part's color row, i % ncolors
+        int i = c0;
+        if (parts) {
+            // the parts whose plane i + dq is staged at the pixel's (bx, by) -- all of the pass for
+            // nearly every pixel -- straight from the window: independent LDS reads
+            const unsigned wx = (unsigned)(bx - W.x0), wy = (unsigned)(by - W.y0);
+            const int fast = wx < (unsigned)W.w && wy < (unsigned)W.h
+                                 ? min(c0 + staged, H.count) - dq   // planes c0 .. c0 + staged - 1
+                                 : c0;
+            const float* at = W.win + wy * W.w + wx + dq * W.w * W.h;
+#pragma unroll 4
+            for (; i < fast; ++i) {
+                heat_maps_add(c, at[(i - c0) * W.w * W.h], H.colors + color * 3);
+                color = color + 1 == H.ncolors ? 0 : color + 1;
+            }
+        }
+#pragma unroll 1
+        for (; i < c0 + staged; i += unit) {
+            int ch = H.channel + i, x = bx, y = by;
+            if (parts && i + dq > H.count - 1) {   // past the end of the parts: the stack's last value
+                ch = H.count - 1;
+                x = hw - 1;
+                y = hh - 1;
+            } else if (parts) {
+                ch = i + dq;
+            }
+            float v[kHeatMaxTaps];
+            unsigned miss;
+            if (cubic) miss = heat_gather_window(v, kSampleBicubic, W, ch, x, y, hw, hh);
+            else if (parts) miss = heat_gather_window(v, kSampleOne, W, ch, x, y, hw, hh);
+            else if (bilinear) miss = heat_gather_window(v, kSamplePaf, W, ch, x, y, hw, hh);
+            else miss = heat_gather_window(v, kSamplePafBase, W, ch, x, y, hw, hh);
+            heat_gather_missed(v, miss, S, H, f, ch, x, y);
+            if (cubic) {
+                const float h = heat_bicubic(v, hb.dx, hb.dy);
+                color_heat(c, H.kind == kHeatDistance ? fabsf(h) : h);
+            } else if (parts) {
+                heat_maps_add(c, v[0], H.colors + color * 3);
+                color = color + 1 == H.ncolors ? 0 : color + 1;
+            } else {
+                paf_add(c, v, v + (bilinear ? 4 : 1), hb.dx, hb.dy, bilinear);
+            }
+        }
+    }
+    float px[3] = {b, g, r};
+    blend_bgr(px, c, H.alpha);
+    b = px[0];
+    g = px[1];
+    r = px[2];
+}
+
+// Heat: the heat layer's mode (kHeatModeNone: the keypoint-only kernel carries none of it)
+template <int K, int Heat>
+__global__ __launch_bounds__(256) void render_frames_kernel(const RenderFramesArgs a)
+{
+    __shared__ unsigned short plist[kRenderMaxPeople];
+    __shared__ float4 items[256][4];
+    __shared__ int wcount[4];
+    const int f = blockIdx.z;
+    const RenderTile t = render_tile(a.w, a.h);
+    // 1. the pixel of the output image, in registers from here to the store
+    float b = 0.f, g = 0.f, r = 0.f;
+    if (t.inside && a.blend) {
+        int u[3];
+        output_pixel<K>(u, a.warp, f, t.x, t.y);
+        b = (float)u[0];
+        g = (float)u[1];
+        r = (float)u[2];
+    }
+    // 2. the heat layer; `items` is its window
+    if constexpr (Heat != kHeatModeNone) {
+        render_heat_pixel<Heat>(a.heat, t, f, reinterpret_cast<float*>(items), b, g, r);
+        __syncthreads();   // the keypoint layers rewrite items
+    }
+    // 3. every layer in order on the frame's own people
+    for (int l = 0; l < a.nlayers; ++l) {
+        const RenderFramesLayer& L = a.layer[l];
+        const int first = L.offsets[f], people = L.offsets[f + 1] - first;
+        render_view_pixel(render_view(L.geom, L.total, first, people, L.npairs, L.parts, L.colors,
+                                      L.alpha),
+                          t, plist, items, wcount, b, g, r);
+    }
+    // 4. OpOutputToCvMat's cast
+    const unsigned cb = cast_u8(b, a.cast), cg = cast_u8(g, a.cast), cr = cast_u8(r, a.cast);
+    if (!a.dst_aligned) {
+        if (t.inside) {
+            uint8_t* d = a.dst + ((size_t)f * a.h + t.y) * a.dst_step + (size_t)t.x * 3;
+            d[0] = (uint8_t)cb;
+            d[1] = (uint8_t)cg;
+            d[2] = (uint8_t)cr;
+        }
+        return;
+    }
+    // rows on 4-byte boundaries (a tile starts at byte 96 * blockIdx.x of its rows): the tile's
+    // 8 x 96 bytes go through LDS -- `items` is idle, every use of it ended at a barrier -- and
+    // leave as 4-byte stores, 24 lanes a row; a row's last 1..3 bytes, if any, as bytes
+    uint8_t* stage = reinterpret_cast<uint8_t*>(items);
+    uint8_t* mine = stage + threadIdx.x * 3;   // (threadIdx.x / 32) * 96 + (threadIdx.x % 32) * 3
+    mine[0] = (uint8_t)cb;
+    mine[1] = (uint8_t)cg;
+    mine[2] = (uint8_t)cr;
+    __syncthreads();
+    const int tx0 = blockIdx.x * kTileW, ty0 = blockIdx.y * kTileH;
+    const int rows = min(kTileH, a.h - ty0), row_bytes = min(kTileW, a.w - tx0) * 3;
+    const int row = threadIdx.x / 24, o = (threadIdx.x % 24) * 4;
+    if (row < rows && o < row_bytes) {   // row < 8 only for threadIdx.x < 192
+        uint8_t* d = a.dst + ((size_t)f * a.h + ty0 + row) * a.dst_step + (size_t)tx0 * 3 + o;
+        const uint8_t* s = stage + row * (kTileW * 3) + o;
+        if (o + 4 <= row_bytes) {
+            *reinterpret_cast<unsigned*>(d) = *reinterpret_cast<const unsigned*>(s);
+        } else {
+            for (int i = 0; i < row_bytes - o; ++i) d[i] = s[i];
+        }
+    }
 }
 
 dim3 tiles(int w, int h)
@@ -740,14 +1027,68 @@ void launch_render_frames(const RenderFramesArgs& args, hipStream_t stream)
         OPK_CHECK_ARG(a.layer[l].offsets && (a.layer[l].total == 0 || a.layer[l].geom),
                       "NULL layer");
     check_warp(a.warp, a.w, a.h);
+    RenderFramesHeat& H = a.heat;
+    const bool heat = H.kind != kHeatNone;
+    if (heat) {
+        OPK_CHECK_ARG(H.kind >= kHeatPart && H.kind <= kHeatDistance, "unknown heat kind");
+        OPK_CHECK_ARG(a.blend, "the heat layer blends with the frame");
+        const HeatMap& M = H.map;
+        OPK_CHECK_ARG(M.w > 0 && M.h > 0 && M.channels > 0, "empty heat map");
+        OPK_CHECK_ARG(M.heat || (M.nsrc >= 1 && M.nsrc <= kMaxResizeSources), "heat map sources");
+        // plane indices and a plane's offsets (the all-parts render's reaches area + w) are ints
+        OPK_CHECK_ARG((size_t)M.w * M.h <= (1u << 30) &&
+                          (size_t)a.n * M.channels <= (size_t)INT32_MAX,
+                      "heat stack too large");
+        const bool pair = H.kind == kHeatPaf || H.kind == kHeatPafs;
+        const int first = H.kind == kHeatParts ? 0 : H.channel;
+        const int used = H.kind == kHeatParts ? H.count : (pair ? 2 * H.count : 1);
+        OPK_CHECK_ARG(H.count >= 1 || !(pair || H.kind == kHeatParts), "no channel to draw");
+        OPK_CHECK_ARG(first >= 0 && used <= M.channels - first, "channel outside the heat stack");
+        OPK_CHECK_ARG(H.kind != kHeatParts || (H.colors && H.ncolors > 0), "NULL colors");
+        // RENDER_HEAT_STAGE=0 (dev A/B): every pixel evaluates its own samples
+        H.staged = dev_switch("RENDER_HEAT_STAGE", 1) != 0 &&
+                   render_heat_staged(H.kind == kHeatPafs && H.count == 1 ? kHeatPaf : H.kind, H.scale);
+    }
     const dim3 grid = batch_tiles(a.w, a.h, a.n), block(kTileW * kTileH);
+#define OPK_LAUNCH_FRAMES_MODE(K, M) \
+    hipLaunchKernelGGL((render_frames_kernel<K, M>), grid, block, 0, stream, a)
+#define OPK_LAUNCH_FRAMES(K)                                                                       \
+    do {                                                                                           \
+        if (!heat)                                                                                 \
+            OPK_LAUNCH_FRAMES_MODE(K, kHeatModeNone);                                              \
+        else if (H.kind == kHeatPart || H.kind == kHeatDistance)                                   \
+            OPK_LAUNCH_FRAMES_MODE(K, kHeatModeCubic);                                             \
+        else if (H.kind == kHeatParts)                                                             \
+            OPK_LAUNCH_FRAMES_MODE(K, kHeatModeParts);                                             \
+        else                                                                                       \
+            OPK_LAUNCH_FRAMES_MODE(K, kHeatModePaf);                                               \
+    } while (0)
     if (a.warp.ksize == 0)
-        hipLaunchKernelGGL(render_frames_kernel<0>, grid, block, 0, stream, a);
+        OPK_LAUNCH_FRAMES(0);
     else if (a.warp.ksize == 2)
-        hipLaunchKernelGGL(render_frames_kernel<2>, grid, block, 0, stream, a);
+        OPK_LAUNCH_FRAMES(2);
     else
-        hipLaunchKernelGGL(render_frames_kernel<4>, grid, block, 0, stream, a);
+        OPK_LAUNCH_FRAMES(4);
+#undef OPK_LAUNCH_FRAMES_MODE
+#undef OPK_LAUNCH_FRAMES
     OPK_LAUNCH_CHECK();
+}
+
+bool render_heat_staged(int kind, float scale)
+{
+    // heat_window's rectangle: the bases of a tile's first and last pixel are at most
+    // floor(31 / scale) + 1 (8 rows: floor(7 / scale) + 1) apart -- one more allows for the
+    // rounding of the two source coordinates --, plus the kind's taps
+    int taps = 0, planes = 1;
+    if (kind == kHeatPart || kind == kHeatDistance) taps = 3;
+    else if (kind == kHeatParts) taps = 1;
+    else if (kind == kHeatPaf) taps = 1, planes = 2;
+    else if (kind == kHeatPafs) planes = 2;
+    else return false;
+    if (!(scale > 0.f) || !std::isfinite(scale)) return false;
+    const double w = std::floor((kTileW - 1) / (double)scale) + 3 + taps;
+    const double h = std::floor((kTileH - 1) / (double)scale) + 3 + taps;
+    return w * h * planes <= kRenderHeatWindow;
 }
 
 void launch_render_heat_map(const RenderHeatArgs& a, int part, bool abs_value, hipStream_t stream)
