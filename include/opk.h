@@ -291,7 +291,23 @@ int opk_net_flops_per_frame(opk_net* net, int h, int w, double* flops);
  *   fusion.  Re-plans the net's shapes; loaded weights are kept. */
 #define OPK_PRECISION_FP16 0
 #define OPK_PRECISION_SPLIT 1
-int opk_net_set_precision(opk_net* net, int precision);
+int opk_net_set_precision(opk_net* net, int precision);   /* the uniform schedule */
+/* Per-layer precision: one OPK_PRECISION_FP16 / OPK_PRECISION_SPLIT per conv, in
+ * opk_net_conv_info order.  An fp16 conv reads the hi image of whatever it reads and writes hi
+ * only; a split conv reads hi and lo and writes both.  A buffer has a lo twin iff a split conv (or
+ * a pool fed by one) writes part of it; the lo channels under an fp16 writer stay zero.  A split
+ * conv whose whole source was written by fp16 convs ("hi-only") runs two products per chunk
+ * (x_hi w_lo + x_hi w_hi) on the hi-only instantiations of the generic kernel (3x3 and 1x1 tiles,
+ * the small-batch 3x3 tiles; launch-log names ending ",split,xhi>") and reads no twin; where the
+ * kernel that runs it has none (7x7, the persistent 8-wave kernel, a pooled epilogue, a fused head
+ * pair) it runs the three-product kernel over a zero twin -- equal values.  The conv1 fusion needs
+ * both of its convs fp16; a head pair runs fused only with equal precisions; a pool follows its
+ * input.  Uniform schedules plan, launch and compute exactly as opk_net_set_precision.
+ * count != opk_net_num_convs or any other value: OPK_ERR_ARG (the message names the index) and the
+ * schedule in force stays.  Re-packs the convs whose precision changes and re-plans the shapes;
+ * loaded weights are kept. */
+int opk_net_set_precision_schedule(opk_net* net, const int* precisions, int count);
+int opk_net_conv_precision(opk_net* net, int index);   /* -1 for NULL or a bad index */
 /* Small-batch mode (no reference counterpart).  The default planning tiles every 3x3 and 7x7 conv
  * for the large batches of opk_pose_submit (256 or 512 positions x 64..128 outputs): a forward of
  * one frame, as op::PoseExtractorCaffe::forwardPass runs it, or of a few face / hand crops, leaves
@@ -343,6 +359,12 @@ int opk_net_output(opk_net* net, float** output_dev, int shape[4]);
  * fused head pair) fail with the "kept on chip" message. */
 int opk_net_blob(opk_net* net, const char* name, int frame0, int nframes, float* host_out,
                  int shape[4]);
+/* The same blob as stored: the hi image and its lo twin, each fp32 NCHW [nframes][channels][h][w]
+ * (opk_net_blob returns hi + lo where the buffer has a twin, else hi).  A buffer without a twin
+ * (no split writer): lo is zeros and *has_lo = 0.  net_output: hi is the fp32 value.  Either
+ * plane pointer may be NULL; fails for the same "kept on chip" blobs as opk_net_blob. */
+int opk_net_blob_planes(opk_net* net, const char* name, int frame0, int nframes, float* hi_host,
+                        float* lo_host, int shape[4], int* has_lo);
 /* Kernels launched by the last forward run while the dev switch LAUNCH_LOG was 1, one
  * "<layer>\t<kernel instantiation>\n" line per launch.  *needed = bytes incl. the NUL; the text
  * is copied when size >= *needed. */

@@ -89,6 +89,9 @@ _SIGS = {
     "opk_pose_read_timing": (_i, [_p, _ip, _c.POINTER(_d)]),
     "opk_pose_read_collect_times": (_i, [_p, _ip, _c.POINTER(_d), _c.POINTER(_d), _ip]),
     "opk_net_set_precision": (_i, [_p, _i]),
+    "opk_net_set_precision_schedule": (_i, [_p, _ip, _i]),
+    "opk_net_conv_precision": (_i, [_p, _i]),
+    "opk_net_blob_planes": (_i, [_p, _c.c_char_p, _i, _i, _p, _p, _ip, _ip]),
     "opk_net_set_small_batch": (_i, [_p, _i]),
     "opk_net_small_batch": (_i, [_p]),
     "opk_net_conv_plan": (_i, [_p, _i, _i, _i, _i, _i, _ip, _ip, _ip, _ip]),

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, int4
+from ._lib import OpkError, check, int4
 from .pose_tables import (BODY_25, CONNECT_CPU, CONNECT_GPU, CONNECT_INTER_MIN_ABOVE_THRESHOLD,
                           CONNECT_INTER_THRESHOLD,
                           CONNECT_MIN_SUBSET_CNT, CONNECT_MIN_SUBSET_SCORE, NMS_THRESHOLD)
@@ -568,6 +568,31 @@ class Net:
         the MFMA work; opk_net_set_precision)."""
         check(self.L.opk_net_set_precision(self.h, int(precision)))
 
+    def set_precision_schedule(self, schedule):
+        """Per-layer precision (opk_net_set_precision_schedule).  schedule: a sequence of one
+        PRECISION_FP16 / PRECISION_SPLIT per conv in convs() order; a {conv name: precision} dict
+        (convs it does not name keep theirs); or a callable taking a convs() entry (plus its
+        "index") and returning the precision.  Refused schedules leave the one in force."""
+        convs = self.convs()
+        if callable(schedule):
+            sched = [schedule(dict(c, index=i)) for i, c in enumerate(convs)]
+        elif isinstance(schedule, dict):
+            names = {c["name"] for c in convs}
+            unknown = sorted(set(schedule) - names)
+            if unknown:
+                raise OpkError("precision schedule: no convolution named " + ", ".join(unknown))
+            cur = self.precision_schedule()
+            sched = [schedule.get(c["name"], cur[i]) for i, c in enumerate(convs)]
+        else:
+            sched = list(schedule)
+        arr = (ctypes.c_int * max(1, len(sched)))(*[int(p) for p in sched])
+        check(self.L.opk_net_set_precision_schedule(self.h, arr, len(sched)))
+
+    def precision_schedule(self):
+        """The precision of every conv, in convs() order."""
+        return [self.L.opk_net_conv_precision(self.h, i)
+                for i in range(self.L.opk_net_num_convs(self.h))]
+
     def set_small_batch(self, on=True):
         """Small-batch mode (opk_net_set_small_batch): 3x3 layers that would not fill the chip run
         on conv3s tiles; the results are bit-identical."""
@@ -631,6 +656,21 @@ class Net:
         check(self.L.opk_net_blob(self.h, name.encode(), f0, nf,
                                   out.ctypes.data_as(ctypes.c_void_p), shape))
         return out
+
+    def blob_planes(self, name, frames=None):
+        """(hi, lo, has_lo) of a named top of the last forward (opk_net_blob_planes): the stored hi
+        image and its lo twin as fp32 NCHW numpy; a buffer without a twin gives zeros and False."""
+        shape = (ctypes.c_int * 4)()
+        has = ctypes.c_int()
+        f0, nf = frames if frames is not None else (0, self.output()[1][0])
+        check(self.L.opk_net_blob_planes(self.h, name.encode(), f0, nf, None, None, shape,
+                                         ctypes.byref(has)))
+        hi = np.empty(tuple(shape), np.float32)
+        lo = np.empty(tuple(shape), np.float32)
+        check(self.L.opk_net_blob_planes(self.h, name.encode(), f0, nf,
+                                         hi.ctypes.data_as(ctypes.c_void_p),
+                                         lo.ctypes.data_as(ctypes.c_void_p), shape, ctypes.byref(has)))
+        return hi, lo, bool(has.value)
 
     def launch_log(self):
         """[(layer, kernel instantiation)] of the last forward run under dev_switches(LAUNCH_LOG=1)."""

@@ -135,6 +135,15 @@ int opk_net_blob(opk_net* net, const char* name, int frame0, int nframes, float*
     });
 }
 
+int opk_net_blob_planes(opk_net* net, const char* name, int frame0, int nframes, float* hi_host,
+                        float* lo_host, int shape[4], int* has_lo)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(net && name && shape && has_lo, "NULL argument");
+        net->net->blob_planes(name, frame0, nframes, hi_host, lo_host, shape, has_lo);
+    });
+}
+
 int opk_net_launch_log(opk_net* net, char* buf, size_t size, size_t* needed)
 {
     return guarded_net([&] {
@@ -403,6 +412,20 @@ int opk_net_set_precision(opk_net* net, int precision)
         OPK_CHECK_ARG(net, "NULL net");
         net->net->set_precision(precision);
     });
+}
+
+int opk_net_set_precision_schedule(opk_net* net, const int* precisions, int count)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(net, "NULL net");
+        net->net->set_precision_schedule(precisions, count);
+    });
+}
+
+int opk_net_conv_precision(opk_net* net, int index)
+{
+    if (!net) return -1;
+    return net->net->conv_precision(index);
 }
 
 int opk_net_set_small_batch(opk_net* net, int enable)

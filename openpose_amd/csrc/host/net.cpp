@@ -323,12 +323,36 @@ void NetHip::set_conv(const std::string& name, const float* w, const float* b, c
 void NetHip::set_precision(int precision)
 {
     OPK_CHECK_ARG(precision == kPrecisionFp16 || precision == kPrecisionSplit, "unknown precision");
-    if (precision == precision_) return;
-    precision_ = precision;
-    for (auto& c : convs_)
+    const std::vector<int> uniform(convs_.size(), precision);
+    set_precision_schedule(uniform.data(), (int)uniform.size());
+}
+
+void NetHip::set_precision_schedule(const int* precisions, int count)
+{
+    OPK_CHECK_ARG(precisions != nullptr, "NULL schedule");
+    OPK_CHECK_ARG(count == (int)convs_.size(),
+                  "precision schedule: " + std::to_string(count) + " entries for " +
+                      std::to_string(convs_.size()) + " convolutions");
+    for (int i = 0; i < count; ++i)
+        OPK_CHECK_ARG(precisions[i] == kPrecisionFp16 || precisions[i] == kPrecisionSplit,
+                      "precision schedule: unknown precision " + std::to_string(precisions[i]) +
+                          " at index " + std::to_string(i) + " (" + convs_[i].info.name + ")");
+    bool changed = false;
+    for (int i = 0; i < count; ++i) {
+        ConvPlan& c = convs_[i];
+        if (c.precision == precisions[i]) continue;
+        c.precision = precisions[i];
         if (c.loaded) pack(c);
-    shapes_.clear();
+        changed = true;
+    }
+    if (!changed) return;
+    shapes_.clear();   // new twins, launch arguments and kernels
     cur_ = nullptr;
+}
+
+int NetHip::conv_precision(int index) const
+{
+    return index >= 0 && index < (int)convs_.size() ? convs_[index].precision : -1;
 }
 
 void NetHip::set_small_batch(bool on)
@@ -342,8 +366,9 @@ void NetHip::set_small_batch(bool on)
 bool NetHip::fused1_at(int h, int w) const
 {
     // CONV1_FUSED=0 (opk_dev_set, A/B tests): the three separate kernels instead of the fusion
-    // (split precision: no conv1 fusion)
-    return precision_ != kPrecisionSplit && fuse1_.a >= 0 && dev_switch("CONV1_FUSED", 1) != 0 &&
+    // (split precision: no conv1 fusion -- both of its convs must be fp16)
+    return fuse1_.a >= 0 && convs_[fuse1_.a].precision == kPrecisionFp16 &&
+           convs_[fuse1_.b].precision == kPrecisionFp16 && dev_switch("CONV1_FUSED", 1) != 0 &&
            border_ == 1 && conv1_fused_supported(h, w, 64, 64);
 }
 
@@ -358,19 +383,44 @@ NetHip::Dispatch NetHip::dispatch(int n, int h, int w, int cus) const
         D.lh[l] = (D.lh[l - 1] - 2 + 1) / 2 + 1;
         D.lw[l] = (D.lw[l - 1] - 2 + 1) / 2 + 1;
     }
-    D.split = precision_ == kPrecisionSplit;
+    D.csplit.assign(convs_.size(), 0);
+    for (size_t ci = 0; ci < convs_.size(); ++ci) D.csplit[ci] = convs_[ci].precision == kPrecisionSplit;
     D.fused1 = fused1_at(h, w);
     // HEAD_FUSE=0 (opk_dev_set, A/B tests): Mconv6 and Mconv7 as two conv3 launches
     // Positions are decoded by float-reciprocal division in conv_head_kernel: larger batches run
     // the pairs unfused.
     // (split precision: conv_head_kernel's split instantiations; HEAD_FUSE_SPLIT=0, dev A/B: the
     // unfused split pair)
-    D.fusedh = (!D.split || dev_switch("HEAD_FUSE_SPLIT", 1) != 0) && !heads_.empty() &&
-               dev_switch("HEAD_FUSE", 1) != 0;
+    // A pair runs fused only where both convs have one precision: the fp16 or the split
+    // instantiation; a mixed pair runs as two launches.
+    bool heads_fit = dev_switch("HEAD_FUSE", 1) != 0;
     for (const auto& fh : heads_) {
         const int L = convs_[fh.a].level;
-        D.fusedh = D.fusedh && conv_positions_fit((long)n * (D.lh[L] + 2) * (D.lw[L] + 2));
+        heads_fit = heads_fit && conv_positions_fit((long)n * (D.lh[L] + 2) * (D.lw[L] + 2));
     }
+    D.headfused.assign(heads_.size(), 0);
+    for (size_t hi = 0; hi < heads_.size(); ++hi) {
+        const bool sa = D.csplit[heads_[hi].a], sb = D.csplit[heads_[hi].b];
+        D.headfused[hi] = heads_fit && sa == sb && (!sa || dev_switch("HEAD_FUSE_SPLIT", 1) != 0);
+    }
+    // Channels with a split writer, per buffer: a split conv's slices, and the whole output of a
+    // pool whose input has some.  Each channel of a buffer has one writer, whose precision holds
+    // for the life of the plan, and the plan's memset zeroed the twin: the lo channels under an
+    // fp16 writer stay zero, no stale lo can survive.
+    std::vector<std::vector<std::pair<int, int>>> lo_ranges(bufs_.size());
+    for (size_t ci = 0; ci < convs_.size(); ++ci)
+        if (D.csplit[ci])
+            for (const auto& o : convs_[ci].outs)
+                lo_ranges[o.buf].emplace_back(o.coff, o.coff + convs_[ci].info.cout);
+    for (const auto& p : pools_)
+        if (!lo_ranges[p.in_buf].empty()) lo_ranges[p.out_buf].emplace_back(0, bufs_[p.out_buf].cs);
+    D.twin.assign(bufs_.size(), 0);
+    for (size_t b = 0; b < bufs_.size(); ++b) D.twin[b] = !lo_ranges[b].empty();
+    auto source_has_lo = [&](const ConvPlan& c) {
+        for (const auto& r : lo_ranges[c.in.buf])
+            if (r.first < c.in.coff + c.cin_pad && c.in.coff < r.second) return true;
+        return false;
+    };
     D.poolfused.assign(pools_.size(), 0);
     D.query.assign(convs_.size(), Conv3Query{});
     D.conv.assign(convs_.size(), Conv3Plan{});
@@ -391,7 +441,9 @@ NetHip::Dispatch NetHip::dispatch(int n, int h, int w, int cus) const
             q.dst_coff[d] = c.outs[d].coff;
         }
         q.out32 = c.out32_coff >= 0;
-        q.split = D.split;
+        q.split = D.csplit[ci];
+        // a split conv whose source has no split writer ("hi-only"): the two-product kernel
+        q.xhi = q.split && !source_has_lo(c);
         q.sink = true;
         q.cus = cus;
         // small-batch mode: 3x3 and 7x7 convs that run as launches of their own (the fused units
@@ -413,8 +465,19 @@ NetHip::Dispatch NetHip::dispatch(int n, int h, int w, int cus) const
                 D.poolfused[p] = 1;
             }
         }
+        // a fused head pair runs conv_head_kernel, which has no hi-only instantiation
+        if (c.head >= 0 && D.headfused[c.head]) q.xhi = false;
         D.conv[ci] = conv3_plan(q);
+        // no hi-only instantiation for what runs (7x7, conv3w8, a pooled epilogue, conv_head;
+        // SPLIT_XHI=0): the three-product kernel over a zero twin, which the plan allocates
+        if (q.split && !D.conv[ci].xhi && !source_has_lo(c)) {
+            q.xhi = false;
+            D.twin[c.in.buf] = 1;
+        }
     }
+    // a pool follows its input: the split kernel iff the input has a twin, and then writes one
+    for (const auto& p : pools_)
+        if (D.twin[p.in_buf]) D.twin[p.out_buf] = 1;
     return D;
 }
 
@@ -439,7 +502,7 @@ std::vector<std::string> NetHip::conv_kernels(int index, int n, int h, int w, in
     const Dispatch D = dispatch(n, h, w, cus);
     if (D.fused1 && (index == fuse1_.a || index == fuse1_.b))
         return index == fuse1_.a ? std::vector<std::string>{kConv1FusedKernel} : std::vector<std::string>{};
-    if (D.fusedh && c.head >= 0)
+    if (c.head >= 0 && D.headfused[c.head])
         return index == heads_[c.head].a ? std::vector<std::string>{kConvHeadKernel} : std::vector<std::string>{};
     if (c.from_image) return {kConvImageKernel};
     std::vector<std::string> out;
@@ -460,7 +523,7 @@ void NetHip::pack(ConvPlan& c)
     const float* w = c.hw.data();
     const float* b = c.hb.data();
     const float* slope = c.hs.empty() ? nullptr : c.hs.data();
-    const bool split = precision_ == kPrecisionSplit;
+    const bool split = c.precision == kPrecisionSplit;
     const int K = c.ksteps * kConvBK;
     const int cin = c.info.cin, k = c.info.k;
     const bool need_packed = c.from_image;   // conv_image's layout: [cout_pad][64]
@@ -638,8 +701,9 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
         // conv_image reads the NCHW input itself (in both precisions)
         if ((int)i == image_buf_) continue;
         bool head_buf = false;
-        for (const auto& fh : heads_) head_buf = head_buf || fh.buf == (int)i;
-        if (S.fusedh && head_buf) continue;   // Mconv6 outputs live only inside conv_head_kernel
+        for (size_t hi = 0; hi < heads_.size(); ++hi)
+            head_buf = head_buf || (S.headfused[hi] && heads_[hi].buf == (int)i);
+        if (head_buf) continue;   // Mconv6 outputs live only inside conv_head_kernel
         if (S.fused1 && ((int)i == fuse1_.abuf || (int)i == fuse1_.bbuf))
             continue;   // conv1_1 / conv1_2 outputs live only inside conv1_fused_kernel
         bool pooled_away = false;
@@ -657,7 +721,7 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
         // zeroed on the stream whose kernels read the plan first
         OPK_HIP(hipMemsetAsync(raw, 0, bytes, zero_stream ? zero_stream : ctx_->stream));
         ptr[i] = raw + head * bufs_[i].cs;
-        if (S.split) {   // the lo twin: same layout, zeroed borders and guards
+        if (S.twin[i]) {   // the lo twin: same layout, zeroed borders and guards
             uint16_t* rl = static_cast<uint16_t*>(S.mem_lo.back()->get(bytes));
             OPK_HIP(hipMemsetAsync(rl, 0, bytes, zero_stream ? zero_stream : ctx_->stream));
             S.base_lo[i] = rl + head * bufs_[i].cs;
@@ -708,17 +772,19 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
             a.dst[d] = ptr[c.outs[d].buf];
             a.dst_cs[d] = bufs_[c.outs[d].buf].cs;
             a.dst_coff[d] = c.outs[d].coff;
-            a.dst_lo[d] = S.base_lo[c.outs[d].buf];
+            // (an fp16 conv writes hi only: the twin's channels, if any, stay zero)
+            a.dst_lo[d] = S.csplit[ci] ? S.base_lo[c.outs[d].buf] : nullptr;
         }
-        a.split = S.split ? 1 : 0;
-        a.wscale = S.split ? c.wscale : 1.f;
-        a.in_lo = S.base_lo[c.in.buf];
+        a.split = S.csplit[ci] ? 1 : 0;
+        a.wscale = S.csplit[ci] ? c.wscale : 1.f;
+        // (no lo pointer: the hi-only plan, as conv3_query reads it)
+        a.in_lo = S.csplit[ci] && use3 && !S.query[ci].xhi ? S.base_lo[c.in.buf] : nullptr;
         for (size_t q = 0; q < pools_.size(); ++q)
             if (S.poolfused[q] && pool_conv_[q] == (int)ci) {   // the pooled image instead
                 a.pool = 1;
                 a.ndst = 1;
                 a.dst[0] = ptr[pools_[q].out_buf];
-                a.dst_lo[0] = S.base_lo[pools_[q].out_buf];   // (split precision: its lo twin)
+                a.dst_lo[0] = S.csplit[ci] ? S.base_lo[pools_[q].out_buf] : nullptr;   // (split precision: its lo twin)
                 a.dst_cs[0] = bufs_[pools_[q].out_buf].cs;
                 a.dst_coff[0] = 0;
             }
@@ -795,6 +861,19 @@ void NetHip::forward_on(const float* input, int n, int h, int w, hipStream_t st,
 
 void NetHip::blob(const std::string& name, int f0, int nf, float* host, int shape[4]) const
 {
+    read_planes(name, f0, nf, nullptr, nullptr, host, shape, nullptr);
+}
+
+void NetHip::blob_planes(const std::string& name, int f0, int nf, float* hi, float* lo, int shape[4],
+                         int* has_lo) const
+{
+    read_planes(name, f0, nf, hi, lo, nullptr, shape, has_lo);
+}
+
+// hi / lo: the stored planes; sum: the value, hi + lo where the buffer has a twin, else hi
+void NetHip::read_planes(const std::string& name, int f0, int nf, float* hi, float* lo, float* sum,
+                         int shape[4], int* has_lo) const
+{
     OPK_CHECK_ARG(cur_ != nullptr, "no forward yet");
     const auto it = blob_loc_.find(name);
     OPK_CHECK_ARG(it != blob_loc_.end(), "no blob named " + name);
@@ -805,26 +884,30 @@ void NetHip::blob(const std::string& name, int f0, int nf, float* host, int shap
     if (shape) {
         shape[0] = nf; shape[1] = L.ch; shape[2] = H; shape[3] = W;
     }
-    if (!host) return;
+    const bool twin = !L.out32 && S.base_lo[L.buf] != nullptr;
+    if (has_lo) *has_lo = twin ? 1 : 0;
+    if (!hi && !lo && !sum) return;
     ctx_->bind();
     OPK_HIP(hipStreamSynchronize(ctx_->stream));
     const size_t hw = (size_t)H * W;
     if (L.out32) {
         OPK_CHECK_ARG(L.level == out_level_, name + ": not at the output resolution");
-        for (int f = 0; f < nf; ++f)
-            OPK_HIP(hipMemcpy(host + (size_t)f * L.ch * hw,
-                              S.out() + ((size_t)(f0 + f) * out_c_ + L.coff) * hw,
-                              (size_t)L.ch * hw * 4, hipMemcpyDeviceToHost));
+        for (float* host : {hi, sum})
+            for (int f = 0; f < nf && host; ++f)
+                OPK_HIP(hipMemcpy(host + (size_t)f * L.ch * hw,
+                                  S.out() + ((size_t)(f0 + f) * out_c_ + L.coff) * hw,
+                                  (size_t)L.ch * hw * 4, hipMemcpyDeviceToHost));
+        if (lo) std::fill(lo, lo + (size_t)nf * L.ch * hw, 0.f);
         return;
     }
     OPK_CHECK_ARG(S.base[L.buf] != nullptr,
                   name + ": kept on chip by a fused kernel (not materialised at this shape)");
     const int B = border_, Wp = W + 2 * B, Hp = H + 2 * B, cs = bufs_[L.buf].cs;
     const size_t frame_elems = (size_t)Hp * Wp * cs;
-    std::vector<uint16_t> raw(frame_elems * nf), rlo(S.split ? frame_elems * nf : 0);
+    std::vector<uint16_t> raw(frame_elems * nf), rlo(twin ? frame_elems * nf : 0);
     OPK_HIP(hipMemcpy(raw.data(), S.base[L.buf] + (size_t)f0 * frame_elems, raw.size() * 2,
                       hipMemcpyDeviceToHost));
-    if (S.split)   // split precision: the value is hi + lo
+    if (twin)   // split precision: the value is hi + lo
         OPK_HIP(hipMemcpy(rlo.data(), S.base_lo[L.buf] + (size_t)f0 * frame_elems, rlo.size() * 2,
                           hipMemcpyDeviceToHost));
     for (int f = 0; f < nf; ++f)
@@ -832,10 +915,14 @@ void NetHip::blob(const std::string& name, int f0, int nf, float* host, int shap
             for (int x = 0; x < W; ++x) {
                 const size_t at = f * frame_elems + ((size_t)(y + B) * Wp + x + B) * cs + L.coff;
                 const uint16_t* src = raw.data() + at;
-                for (int c = 0; c < L.ch; ++c)
-                    host[((size_t)f * L.ch + c) * hw + (size_t)y * W + x] =
-                        (float)__builtin_bit_cast(_Float16, src[c]) +
-                        (S.split ? (float)__builtin_bit_cast(_Float16, rlo[at + c]) : 0.f);
+                for (int c = 0; c < L.ch; ++c) {
+                    const size_t o = ((size_t)f * L.ch + c) * hw + (size_t)y * W + x;
+                    const float vh = (float)__builtin_bit_cast(_Float16, src[c]);
+                    const float vl = twin ? (float)__builtin_bit_cast(_Float16, rlo[at + c]) : 0.f;
+                    if (hi) hi[o] = vh;
+                    if (lo) lo[o] = vl;
+                    if (sum) sum[o] = vh + vl;
+                }
             }
 }
 
@@ -933,7 +1020,7 @@ void NetHip::forward_steps(ShapePlan& S, const float* input, int n, int h, int w
         if (s.conv) {
             const ConvPlan& c = convs_[s.idx];
             const ConvArgs& a = S.args[s.idx];
-            if (S.fusedh && c.head >= 0 && heads_[c.head].step == (int)si) {
+            if (c.head >= 0 && S.headfused[c.head] && heads_[c.head].step == (int)si) {
                 const FuseHead& fh = heads_[c.head];
                 const ConvPlan& cb = convs_[fh.b];
                 const ConvArgs& b = S.args[fh.b];
@@ -965,7 +1052,7 @@ void NetHip::forward_steps(ShapePlan& S, const float* input, int n, int h, int w
                 h.out32_coff = b.out32_coff;
                 // persistent grid (HEAD_PERSIST=0: one workgroup per tile, dev A/B)
                 h.cus = dev_switch("HEAD_PERSIST", 1) != 0 ? a.cus : 0;
-                if (S.split) {
+                if (S.csplit[s.idx]) {
                     h.split = 1;
                     h.in_lo = a.in_lo;
                     for (int d = 0; d < b.ndst; ++d) h.dst_lo[d] = b.dst_lo[d];
@@ -993,7 +1080,7 @@ void NetHip::forward_steps(ShapePlan& S, const float* input, int n, int h, int w
             const PoolPlan& p = pools_[s.idx];
             const int L = p.level_in;
             if (log) log->layer = "pool";
-            if (S.split)
+            if (S.twin[p.in_buf])
                 launch_maxpool2_split(ptr[p.out_buf], S.base_lo[p.out_buf], ptr[p.in_buf],
                                       S.base_lo[p.in_buf], n, lh_[L], lw_[L], bufs_[p.in_buf].cs,
                                       lh_[L + 1], lw_[L + 1], st, border_);

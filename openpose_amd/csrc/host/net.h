@@ -28,8 +28,22 @@ public:
     // kernels: ~fp32 results at ~3x the MFMA work; ConvArgs::split).  Re-plans the shapes and
     // re-packs the loaded weights.
     static constexpr int kPrecisionFp16 = 0, kPrecisionSplit = 1;
-    void set_precision(int precision);
-    int precision() const { return precision_; }
+    void set_precision(int precision);   // the uniform schedule
+    // Per-layer precision: one kPrecisionFp16 / kPrecisionSplit per conv, in convs() order.  An
+    // fp16 conv reads the hi image of its source and writes hi only (the lo twin of its channels,
+    // where the buffer has one, keeps the zero the plan's memset gave it); a split conv reads hi
+    // and lo and writes both.  Planning rules (dispatch()):
+    //   * a buffer has a lo twin iff a split conv (or a pool fed by one) writes some of its
+    //     channels, or a three-product kernel has to read it (below);
+    //   * a split conv none of whose input channels has a split writer is "hi-only": it runs the
+    //     two-product instantiation (Conv3Plan::xhi) where its tile has one, else the
+    //     three-product kernel over a zero twin the plan allocates for it;
+    //   * conv1 fusion needs both convs fp16; a head pair runs fused only with equal precisions;
+    //     a pool follows its input (split iff the input has a twin).
+    // Refuses (OPK_ERR_ARG, the schedule in force untouched) a wrong count or an unknown value.
+    // Re-packs only the convs whose precision changes and re-plans the shapes.
+    void set_precision_schedule(const int* precisions, int count);
+    int conv_precision(int index) const;   // -1: bad index
     // Small-batch mode (off by default): 3x3 convs whose product geometry gives fewer
     // workgroups than the chip has CUs run on conv3s tiles (conv3_plan, conv.h) -- the same
     // bits, more of the chip busy when a forward is a frame or a few.  Re-plans the shapes.
@@ -99,6 +113,10 @@ public:
     // (conv1_1 / conv1_2 in conv1_fused, a pooled conv's un-pooled output, Mconv6 in conv_head)
     // throw.  host == nullptr: shape only.
     void blob(const std::string& name, int f0, int nf, float* host, int shape[4]) const;
+    // the same, the stored planes apart: the hi image and its lo twin (zeros and *has_lo = 0 where
+    // the buffer has none; the fp32 net output: hi = the value).  Either plane may be nullptr.
+    void blob_planes(const std::string& name, int f0, int nf, float* hi, float* lo, int shape[4],
+                     int* has_lo) const;
     // kernels launched by the last forward run while the dev switch LAUNCH_LOG was 1
     const std::vector<std::string>& launches() const { return log_.lines; }
 
@@ -121,10 +139,13 @@ private:
         bool loaded = false;
         bool slope01 = true;  // PReLU slopes all in [0, 1] (ConvArgs::actmax)
         float wscale = 1.f;   // split precision: 2^-e of the packed weights' scaling (ConvArgs::wscale)
+        int precision = kPrecisionFp16;   // this conv's arithmetic (set_precision_schedule)
         std::vector<float> hw, hb, hs;   // host copies of the weights (re-packed per precision)
     };
     bool fused1_at(int h, int w) const;            // conv1_fused_kernel runs at this input size
-    void pack(ConvPlan& c);   // device layouts of one conv's weights for the current precision
+    void read_planes(const std::string& name, int f0, int nf, float* hi, float* lo, float* sum,
+                     int shape[4], int* has_lo) const;
+    void pack(ConvPlan& c);   // device layouts of one conv's weights for its precision
     struct PoolPlan { int in_buf, out_buf, level_in, channels; };
     struct Step { bool conv; int idx; };
 
@@ -132,9 +153,10 @@ private:
     // any device memory exists (dispatch())
     struct Dispatch {
         std::vector<int> lh, lw;       // size of every pooling level
-        bool split = false;            // planned for kPrecisionSplit: every buffer has a lo twin
+        std::vector<char> csplit;      // per conv: kPrecisionSplit
+        std::vector<char> twin;        // per buffer: has a lo twin
         bool fused1 = false;           // conv1_fused_kernel runs for this shape
-        bool fusedh = false;           // conv_head_kernel runs the fused head pairs
+        std::vector<char> headfused;   // per head pair: conv_head_kernel runs it
         std::vector<char> poolfused;   // per pool: run inside its conv's epilogue (conv3w8 POOL)
         std::vector<Conv3Query> query; // per conv (not the image conv): the whole batch's query
         std::vector<Conv3Plan> conv;   // ... and its plan
@@ -182,7 +204,6 @@ private:
     // (and nothing else reads), -1 none; per input shape it runs fused where conv3w8 supports it
     std::vector<int> pool_conv_;
     int cus_ = 256;               // compute units (persistent-kernel grid)
-    int precision_ = kPrecisionFp16;
     bool small_batch_ = false;    // set_small_batch
     int border_ = 1;              // zero border of every padded image (widest conv pad, >= 1)
 

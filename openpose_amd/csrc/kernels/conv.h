@@ -115,6 +115,9 @@ struct Conv3Query {
     int ndst, dst_cs[kConvMaxDst], dst_coff[kConvMaxDst];   // (pool requested: the pooled image's)
     bool out32;                   // an fp32 NCHW output
     bool split;
+    // split only: the source has no lo twin -- no channel the conv reads has a split writer (a
+    // precision schedule's fp16 -> split boundary, NetHip).  conv3_query: ConvArgs::in_lo == NULL
+    bool xhi;
     bool pool;                    // 2x2/2 max pool in the epilogue requested
     bool small;                   // small-batch tiles requested (NetHip small-batch mode)
     bool sink;                    // scratch for the persistent kernels' masked stores
@@ -130,7 +133,13 @@ struct Conv3Plan {
     int pbn;                      // n-block of the weight packing (conv3s reads conv3's packing)
     bool pool;                    // conv3w8 POOL epilogue (false though requested: not supported)
     bool split;
-    int sw, nstrips, VW;          // strip width and count, virtual row VW = sw + 2 border
+    // the hi-only split instantiation (conv3x_kernel: x_hi w_lo + x_hi w_hi, no lo halo) runs:
+    // asked for (Conv3Query::xhi, dev switch SPLIT_XHI not 0) and the tile has one -- conv3_kernel's
+    // 3x3 and 1x1 tiles, the 3x3 conv3s tiles and conv3w8's non-pooled 96 / 128-output tiles
+    // (conv3w8x_kernel).  false though asked: the three-product kernel, which needs a (zero) lo
+    // twin on the source
+    bool xhi;
+    int sw, nstrips, VW;         // strip width and count, virtual row VW = sw + 2 border
     long total;                   // virtual positions: frames * nstrips * (H + 2 border) * VW
     long grid;                    // workgroups launched
     // the planner's measure of how far the geometry fills the chip: tiles of the GEMM's
@@ -139,13 +148,14 @@ struct Conv3Plan {
     long workgroups;
     bool fits;                    // conv_positions_fit: false -> fewer frames per launch (conv3_run_frames)
     float rcp[3];                 // 1/((H + 2B) VW), 1/VW, 1/nstrips (ConvArgs::rcp)
-    // launch-log name: the whole instantiation for conv3_kernel / conv3s_kernel, up to the
-    // parameters the plan fixes for the persistent kernels ("conv3w8_kernel<BN,NB,POOL")
+    // launch-log name: the whole instantiation for conv3_kernel / conv3s_kernel (hi-only:
+    // "...,split,xhi>"), up to the parameters the plan fixes for the persistent kernels
+    // ("conv3w8_kernel<BN,NB,POOL"; hi-only: "conv3w8x_kernel<BN,NB", logged "...,split,xhi>")
     char name[64];
 };
 // Every decision switch is read here (opk_dev_set; per call, so tests compare variants in one
 // process): CONV3_SMALL, CONV3_W16, CONV3_PERSIST, CONV1_TILE, CONV1_N64W16, CONV3W8_64, SPLIT_W8,
-// CONV3W8N, CONV3W (0 / not), CONV3W8, CONV3S_MAX, CONV7S_BIG.  Throws for sizes no kernel covers.
+// CONV3W8N, CONV3W (0 / not), CONV3W8, CONV3S_MAX, CONV7S_BIG, SPLIT_XHI, SPLIT_XHI_W8.  Throws for sizes no kernel covers.
 // only: a probe tool's choice among the persistent kernels of a conv that supports it (-1: the
 // product rule); plan.family differs from it when the conv does not.
 Conv3Plan conv3_plan(const Conv3Query& q, int only = -1);

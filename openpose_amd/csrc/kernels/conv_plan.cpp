@@ -17,6 +17,8 @@ long ceil_div(long a, long b) { return (a + b - 1) / b; }
 
 int n_block(int cout) { return cout <= 64 ? 64 : (cout <= 96 ? 96 : 128); }
 
+bool want_xhi(const Conv3Query& q) { return q.split && q.xhi && dev_switch("SPLIT_XHI", 1) != 0; }
+
 bool aligned(const Conv3Query& q)   // 16-byte stores of 8-channel groups into every destination
 {
     bool ok = true;
@@ -180,7 +182,14 @@ Conv3Plan product_plan(const Conv3Query& q, int only)
         // pooled: a tile is six whole virtual rows; a multiple of the n-block count (each block
         // keeps one n-block)
         p.grid = std::min<long>(q.cus / p.nb, p.pool ? (p.total / p.VW - 1 + 5) / 6 : ntm) * p.nb;
-        std::snprintf(p.name, sizeof p.name, "conv3w8_kernel<%d,%d,%d", p.bn, p.nb, (int)p.pool);
+        // a split conv over a source without a lo twin: conv3w8x_kernel, the two-product variant of
+        // the non-pooled 96 / 128-output tiles (SPLIT_XHI_W8=0, dev A/B: this family alone on the
+        // three-product kernel over a zero twin)
+        p.xhi = want_xhi(q) && !p.pool && p.bn != 64 && dev_switch("SPLIT_XHI_W8", 1) != 0;
+        if (p.xhi)
+            std::snprintf(p.name, sizeof p.name, "conv3w8x_kernel<%d,%d", p.bn, p.nb);
+        else
+            std::snprintf(p.name, sizeof p.name, "conv3w8_kernel<%d,%d,%d", p.bn, p.nb, (int)p.pool);
     } else if (f == Conv3Family::conv3w) {
         p.grid = std::min<long>(q.cus, ntm);
         std::snprintf(p.name, sizeof p.name, "conv3w_kernel<%d", p.bn);
@@ -195,12 +204,15 @@ Conv3Plan product_plan(const Conv3Query& q, int only)
         } else if (p.ks == 3 && p.nw == 16) {
             p.hr = 704;
         }
+        // a split conv over a source without a lo twin: the two-product instantiation of the 3x3
+        // and 1x1 tiles (SPLIT_XHI=0, opk_dev_set, A/B: the three-product kernel over a zero twin)
+        p.xhi = want_xhi(q) && p.ks != 7;
         if (p.nw == 16)
-            std::snprintf(p.name, sizeof p.name, "conv3_kernel<%d,%d,%d,%d,1,%d,16%s>", p.bm, p.bn, p.hr,
-                          p.tapu, p.ks, q.split ? ",split" : "");
+            std::snprintf(p.name, sizeof p.name, "conv3_kernel<%d,%d,%d,%d,1,%d,16%s%s>", p.bm, p.bn, p.hr,
+                          p.tapu, p.ks, q.split ? ",split" : "", p.xhi ? ",xhi" : "");
         else
-            std::snprintf(p.name, sizeof p.name, "conv3_kernel<%d,%d,%d,%d,%d,%d%s>", p.bm, p.bn, p.hr,
-                          p.tapu, p.minb, p.ks, q.split ? ",8,split" : "");
+            std::snprintf(p.name, sizeof p.name, "conv3_kernel<%d,%d,%d,%d,%d,%d%s%s>", p.bm, p.bn, p.hr,
+                          p.tapu, p.minb, p.ks, q.split ? ",8,split" : "", p.xhi ? ",xhi" : "");
     }
     return p;
 }
@@ -233,12 +245,13 @@ bool small_plan(const Conv3Query& q, Conv3Plan& out)
         measure(s, q, s.hr);
         if (!s.fits || s.bm + (s.ks - 1) * (s.VW + 1) > s.hr) continue;
         // (the 3x3 names as they were: existing launch logs pin them; 7x7: the kernel size last)
+        s.xhi = want_xhi(q) && !k7;   // (the 3x3 tiles have the hi-only instantiation)
         if (k7)
             std::snprintf(s.name, sizeof s.name, "conv3s_kernel<%d,%d,%d,%d,%d%s>", s.bm, s.bn, s.hr,
                           s.tapu, s.ks, q.split ? ",split" : "");
         else
-            std::snprintf(s.name, sizeof s.name, "conv3s_kernel<%d,%d,%d,%d%s>", s.bm, s.bn, s.hr,
-                          s.tapu, q.split ? ",split" : "");
+            std::snprintf(s.name, sizeof s.name, "conv3s_kernel<%d,%d,%d,%d%s%s>", s.bm, s.bn, s.hr,
+                          s.tapu, q.split ? ",split" : "", s.xhi ? ",xhi" : "");
         out = s;
         have = true;
         // CONV7S_BIG (opk_dev_set, tuning): the larger 7x7 tile from a workgroup per this many CUs
@@ -268,6 +281,7 @@ Conv3Query conv3_query(const ConvArgs& a)
     }
     q.out32 = a.out32 != nullptr;
     q.split = a.split != 0;
+    q.xhi = a.split != 0 && a.in_lo == nullptr;
     q.pool = a.pool != 0;
     q.small = a.small != 0;
     q.sink = a.sink != nullptr;
