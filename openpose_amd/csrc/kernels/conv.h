@@ -69,7 +69,7 @@ struct ConvArgs {
     uint16_t* dst_lo[kConvMaxDst];
     float wscale;
     int small;            // planned on conv3s tiles (NetHip small-batch mode): sw / nstrips are the conv3s plan's
-    int pbn;              // conv3s only, set by launch_conv3s: the n-block of the weight packing
+    int pbn;              // conv3s only, set by conv3_planned_args: the n-block of the weight packing
 };
 // the product of a split virtual chunk (3c + k) that reads w_lo: k = 0 (the order above; dev A/B
 // builds: OPK_SPLIT_WLO_K=1, the round-6 order x_hi w_hi, x_hi w_lo, x_lo w_hi, every product
@@ -133,11 +133,10 @@ struct Conv3Plan {
     int pbn;                      // n-block of the weight packing (conv3s reads conv3's packing)
     bool pool;                    // conv3w8 POOL epilogue (false though requested: not supported)
     bool split;
-    // the hi-only split instantiation (conv3x_kernel: x_hi w_lo + x_hi w_hi, no lo halo) runs:
-    // asked for (Conv3Query::xhi, dev switch SPLIT_XHI not 0) and the tile has one -- conv3_kernel's
-    // 3x3 and 1x1 tiles, the 3x3 conv3s tiles and conv3w8's non-pooled 96 / 128-output tiles
-    // (conv3w8x_kernel).  false though asked: the three-product kernel, which needs a (zero) lo
-    // twin on the source
+    // the hi-only split instantiation (template parameter XHI of conv3_kernel / conv3w8_kernel:
+    // x_hi w_lo + x_hi w_hi, no lo halo) runs: asked for (Conv3Query::xhi, dev switch SPLIT_XHI
+    // not 0) and the tile has one (conv_tiles.h: conv3_tile_has_xhi, conv3w8_tile_has_xhi).  false
+    // though asked: the three-product kernel, which needs a (zero) lo twin on the source
     bool xhi;
     int sw, nstrips, VW;         // strip width and count, virtual row VW = sw + 2 border
     long total;                   // virtual positions: frames * nstrips * (H + 2 border) * VW
@@ -150,12 +149,15 @@ struct Conv3Plan {
     float rcp[3];                 // 1/((H + 2B) VW), 1/VW, 1/nstrips (ConvArgs::rcp)
     // launch-log name: the whole instantiation for conv3_kernel / conv3s_kernel (hi-only:
     // "...,split,xhi>"), up to the parameters the plan fixes for the persistent kernels
-    // ("conv3w8_kernel<BN,NB,POOL"; hi-only: "conv3w8x_kernel<BN,NB", logged "...,split,xhi>")
+    // ("conv3w8_kernel<BN,NB,POOL"; hi-only: "conv3w8x_kernel<BN,NB", logged "...,split,xhi>").
+    // These are log names, not symbols: conv3s_kernel<...> and "...,xhi>" are instantiations of
+    // conv3_kernel, conv3w8x_kernel<...> of conv3w8_kernel (XHI = true)
     char name[64];
 };
 // Every decision switch is read here (opk_dev_set; per call, so tests compare variants in one
 // process): CONV3_SMALL, CONV3_W16, CONV3_PERSIST, CONV1_TILE, CONV1_N64W16, CONV3W8_64, SPLIT_W8,
-// CONV3W8N, CONV3W (0 / not), CONV3W8, CONV3S_MAX, CONV7S_BIG, SPLIT_XHI, SPLIT_XHI_W8.  Throws for sizes no kernel covers.
+// CONV3W8N, CONV3W (0 / not), CONV3W8, CONV3S_MAX, CONV7S_BIG, SPLIT_XHI, SPLIT_XHI_W8.  Throws for sizes no kernel covers
+// and for a plan whose tile is not on the list of instantiations (conv_tiles.h): "no instantiation of <name>".
 // only: a probe tool's choice among the persistent kernels of a conv that supports it (-1: the
 // product rule); plan.family differs from it when the conv does not.
 Conv3Plan conv3_plan(const Conv3Query& q, int only = -1);
@@ -183,16 +185,15 @@ constexpr char kConvImageKernel[] = "conv_image_kernel";
 constexpr char kConv1FusedKernel[] = "conv1_fused_kernel";
 constexpr char kConvHeadKernel[] = "conv_head_kernel";
 
-// conv3.hip: the public entry -- plans the conv and launches what the plan says
+// conv3.hip: the public entry -- plans the conv and launches what the plan says.  Families conv3
+// and conv3s are conv3_kernel itself: 7x7, 3x3 and 1x1 tiles of 8 / 16 waves and, for forwards too
+// small to fill the chip with those, 3x3 (any border) and 7x7 (border >= 3) tiles of 4 waves
+// (64 x 32 or 128 x 64; logged as conv3s_kernel<...>), bit-identical to the larger ones
 void launch_conv3(const ConvArgs& a, hipStream_t stream);
 // conv3w.hip: the persistent 512 x {128, 96} 3x3 variant with one mid-unit barrier per K unit
 void launch_conv3w(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
 // conv3w8.hip: the same tile with 8 waves of 64 x BN (fewer LDS fragment reads per MFMA)
 void launch_conv3w8(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
-// conv3.hip: 3x3 (any border) and 7x7 (border >= 3) convs on small tiles (64 x 32 or 128 x 64,
-// conv3_kernel with 4 waves; logged as conv3s_kernel<...>), bit-identical to the kernels above,
-// for forwards too small to fill the chip with the tiles above
-void launch_conv3s(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
 
 // conv_head.hip: Mconv6 (1x1, n1 = 256 / 512 outputs, act6) -> Mconv7 (1x1, n2 <= 64 outputs) in
 // one kernel; the Mconv6 activations never leave the chip.  Input / outputs as ConvArgs (padded

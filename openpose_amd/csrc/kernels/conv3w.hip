@@ -37,6 +37,7 @@
 
 #include "../common.h"
 #include "conv3_dev.h"
+#include "conv_tiles.h"
 
 namespace opk {
 
@@ -530,8 +531,9 @@ void launch_conv3w(const ConvArgs& args, const Conv3Plan& p, hipStream_t stream)
         launched = true;                                                                          \
     }
 #define OPKW_TRY2(BN_, DE_, MX_) OPKW_TRY(BN_, DE_, MX_, true) OPKW_TRY(BN_, DE_, MX_, false)
-    OPKW_TRY2(128, false, false) OPKW_TRY2(128, true, true) OPKW_TRY2(128, true, false)
-    OPKW_TRY2(96, false, false) OPKW_TRY2(96, true, true) OPKW_TRY2(96, true, false)
+#define OPKW_TRY3(BN_) OPKW_TRY2(BN_, false, false) OPKW_TRY2(BN_, true, true) OPKW_TRY2(BN_, true, false)
+    OPK_CONV3W_BNS(OPKW_TRY3)
+#undef OPKW_TRY3
 #undef OPKW_TRY2
 #undef OPKW_TRY
     OPK_CHECK_ARG(launched, std::string("no instantiation of ") + p.name);

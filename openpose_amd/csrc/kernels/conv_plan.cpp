@@ -8,6 +8,7 @@
 #include <cstdio>
 
 #include "../common.h"
+#include "conv_tiles.h"
 
 namespace opk {
 
@@ -18,6 +19,24 @@ long ceil_div(long a, long b) { return (a + b - 1) / b; }
 int n_block(int cout) { return cout <= 64 ? 64 : (cout <= 96 ? 96 : 128); }
 
 bool want_xhi(const Conv3Query& q) { return q.split && q.xhi && dev_switch("SPLIT_XHI", 1) != 0; }
+
+// the plan's family and tile are on the list of what is instantiated (conv_tiles.h)
+void check_instantiated(const Conv3Plan& p)
+{
+    bool on = false, xhi = false;   // (xhi: the tile has a hi-only instantiation)
+    if (p.family == Conv3Family::conv3 || p.family == Conv3Family::conv3s) {
+        for (const Conv3Tile& t : kConv3Tiles)
+            on = on || (p.bm == t.bm && p.bn == t.bn && p.hr == t.hr && p.tapu == t.tapu && p.minb == t.minb &&
+                        p.ks == t.ks && p.nw == t.nw && (p.family == Conv3Family::conv3s) == (t.nw == 4));
+        xhi = conv3_tile_has_xhi(p.ks);
+    } else if (p.family == Conv3Family::conv3w8) {
+        for (const Conv3w8Tile& t : kConv3w8Tiles) on = on || (p.bn == t.bn && p.nb == t.nb && p.pool == t.pool);
+        xhi = conv3w8_tile_has_xhi(p.bn, p.pool);
+    } else {   // conv3w, conv3p: fp16 only
+        for (int bn : kConv3wBNs) on = on || (p.bn == bn && !p.split);
+    }
+    OPK_CHECK_ARG(on && (!p.xhi || (p.split && xhi)), std::string("no instantiation of ") + p.name);
+}
 
 bool aligned(const Conv3Query& q)   // 16-byte stores of 8-channel groups into every destination
 {
@@ -182,10 +201,10 @@ Conv3Plan product_plan(const Conv3Query& q, int only)
         // pooled: a tile is six whole virtual rows; a multiple of the n-block count (each block
         // keeps one n-block)
         p.grid = std::min<long>(q.cus / p.nb, p.pool ? (p.total / p.VW - 1 + 5) / 6 : ntm) * p.nb;
-        // a split conv over a source without a lo twin: conv3w8x_kernel, the two-product variant of
-        // the non-pooled 96 / 128-output tiles (SPLIT_XHI_W8=0, dev A/B: this family alone on the
-        // three-product kernel over a zero twin)
-        p.xhi = want_xhi(q) && !p.pool && p.bn != 64 && dev_switch("SPLIT_XHI_W8", 1) != 0;
+        // a split conv over a source without a lo twin: the two-product (XHI) instantiation where
+        // the tile has one, logged as conv3w8x_kernel (SPLIT_XHI_W8=0, dev A/B: this family alone
+        // on the three-product kernel over a zero twin)
+        p.xhi = want_xhi(q) && conv3w8_tile_has_xhi(p.bn, p.pool) && dev_switch("SPLIT_XHI_W8", 1) != 0;
         if (p.xhi)
             std::snprintf(p.name, sizeof p.name, "conv3w8x_kernel<%d,%d", p.bn, p.nb);
         else
@@ -204,9 +223,9 @@ Conv3Plan product_plan(const Conv3Query& q, int only)
         } else if (p.ks == 3 && p.nw == 16) {
             p.hr = 704;
         }
-        // a split conv over a source without a lo twin: the two-product instantiation of the 3x3
-        // and 1x1 tiles (SPLIT_XHI=0, opk_dev_set, A/B: the three-product kernel over a zero twin)
-        p.xhi = want_xhi(q) && p.ks != 7;
+        // a split conv over a source without a lo twin: the two-product (XHI) instantiation where
+        // the tile has one (SPLIT_XHI=0, opk_dev_set, A/B: the three-product kernel over a zero twin)
+        p.xhi = want_xhi(q) && conv3_tile_has_xhi(p.ks);
         if (p.nw == 16)
             std::snprintf(p.name, sizeof p.name, "conv3_kernel<%d,%d,%d,%d,1,%d,16%s%s>", p.bm, p.bn, p.hr,
                           p.tapu, p.ks, q.split ? ",split" : "", p.xhi ? ",xhi" : "");
@@ -214,28 +233,27 @@ Conv3Plan product_plan(const Conv3Query& q, int only)
             std::snprintf(p.name, sizeof p.name, "conv3_kernel<%d,%d,%d,%d,%d,%d%s%s>", p.bm, p.bn, p.hr,
                           p.tapu, p.minb, p.ks, q.split ? ",8,split" : "", p.xhi ? ",xhi" : "");
     }
+    check_instantiated(p);
     return p;
 }
 
-// conv3s tiles {bm, bn, hr, tapu}: the larger where it gives at least a workgroup per two CUs
-// (7x7: per four, kConv7sBigPerCus) (it stages fewer halo and weight bytes and reads fewer LDS
-// fragments per MFMA), else the smaller
-constexpr int kS_TILES[2][4] = {{64, 32, 256, 9}, {128, 64, 320, 3}};
-// the same two tiles for 7x7 convs, a tap row per K unit: halos of 64 + 6 * 53 and 128 + 6 * 53
-// rows -- a 46-wide crop with its 3 + 3 border columns is one strip
-constexpr int kS_TILES7[2][4] = {{64, 32, 384, 7}, {128, 64, 448, 7}};
-
+// the conv3s tiles of the conv's kernel size (conv_tiles.h, the smaller first): the larger where
+// it gives at least a workgroup per two CUs (7x7: per four, kConv7sBigPerCus) (it stages fewer
+// halo and weight bytes and reads fewer LDS fragments per MFMA), else the smaller
 bool small_plan(const Conv3Query& q, Conv3Plan& out)
 {
     const bool k7 = q.ntaps == 49;
     if (!(k7 ? q.border >= 3 : q.ntaps == 9 && q.border >= 1)) return false;
     bool have = false;
-    for (int k = 1; k >= 0; --k) {
-        const int* tile = k7 ? kS_TILES7[k] : kS_TILES[k];
+    int seen = 0;
+    for (int k = sizeof kConv3Tiles / sizeof kConv3Tiles[0] - 1; k >= 0; --k) {
+        const Conv3Tile& tile = kConv3Tiles[k];
+        if (tile.nw != 4 || tile.ks != (k7 ? 7 : 3)) continue;
+        const bool larger = seen++ == 0;   // (walking the list backwards)
         Conv3Plan s{};
         s.family = Conv3Family::conv3s;
-        s.bm = tile[0]; s.bn = tile[1]; s.hr = tile[2]; s.tapu = tile[3];
-        s.minb = 1; s.ks = k7 ? 7 : 3; s.nw = 4;
+        s.bm = tile.bm; s.bn = tile.bn; s.hr = tile.hr; s.tapu = tile.tapu;
+        s.minb = tile.minb; s.ks = tile.ks; s.nw = tile.nw;
         s.split = q.split;
         s.pbn = n_block(q.cout);
         if (s.pbn % s.bn != 0) continue;
@@ -245,7 +263,7 @@ bool small_plan(const Conv3Query& q, Conv3Plan& out)
         measure(s, q, s.hr);
         if (!s.fits || s.bm + (s.ks - 1) * (s.VW + 1) > s.hr) continue;
         // (the 3x3 names as they were: existing launch logs pin them; 7x7: the kernel size last)
-        s.xhi = want_xhi(q) && !k7;   // (the 3x3 tiles have the hi-only instantiation)
+        s.xhi = want_xhi(q) && conv3_tile_has_xhi(s.ks);
         if (k7)
             std::snprintf(s.name, sizeof s.name, "conv3s_kernel<%d,%d,%d,%d,%d%s>", s.bm, s.bn, s.hr,
                           s.tapu, s.ks, q.split ? ",split" : "");
@@ -256,9 +274,10 @@ bool small_plan(const Conv3Query& q, Conv3Plan& out)
         have = true;
         // CONV7S_BIG (opk_dev_set, tuning): the larger 7x7 tile from a workgroup per this many CUs
         const int per = k7 ? std::max(1, dev_switch("CONV7S_BIG", kConv7sBigPerCus)) : 2;
-        if (k == 1 && per * s.workgroups < std::max(q.cus, 1)) continue;   // (kept if the smaller tile is unsupported)
+        if (larger && per * s.workgroups < std::max(q.cus, 1)) continue;   // (kept if the smaller tile is unsupported)
         break;
     }
+    if (have) check_instantiated(out);
     return have;
 }
 
