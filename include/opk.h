@@ -81,6 +81,7 @@ int opk_memcpy_d2h(opk_ctx* ctx, void* host_dst, const void* dev_src, size_t byt
  * float instantiation's, widened. */
 #define OPK_F32 0
 #define OPK_F64 1
+#define OPK_U8 2   /* a destination type of opk_pose_heatmaps_copy_range only */
 int opk_convert(opk_ctx* ctx, void* dst_dev, int dst_type, const void* src_dev, int src_type,
                 size_t count);
 
@@ -506,6 +507,20 @@ float opk_pose_scale_net_to_output(opk_pose* pose);
 #define OPK_HEATMAP_PAFS 4
 int opk_pose_heatmaps_copy(opk_pose* pose, int types, int scale_mode, float* dst_dev,
                            int shape[4]);
+/* The same values for frames frame0 .. frame0 + nframes - 1 of the collected batch (nframes -1: to
+ * the batch's end), written straight from the net output: one kernel evaluates the resize / merge
+ * (1..8 sources, either map semantics, any upsampling ratio), the channel selection and the
+ * scaling, so the full-resolution stack of opk_pose_heatmaps is neither allocated nor read.
+ * dst_type OPK_F32: bit for bit opk_pose_heatmaps_copy's values.  OPK_U8, ScaleMode UnsignedChar
+ * only (any other mode: OPK_ERR_ARG): min(value, 255) of those floats, which are non-negative
+ * integers (the PAF mapping t * 128.5 + 128.5 reaches 256 and 257 at t = 1; they saturate).
+ * dst_dev [nframes][channels][H][W] device, or NULL to get the shape.  Checked in this order:
+ * the arguments (types, mode, type; frame0 < 0, or nframes neither positive nor -1: a range no
+ * batch holds), OPK_ERR_ARG; then opk_pose_heatmaps' preconditions -- a collected batch and no
+ * later batch in flight -- OPK_ERR_STATE; then the range against the batch, OPK_ERR_ARG.
+ * Complete at return. */
+int opk_pose_heatmaps_copy_range(opk_pose* pose, int types, int scale_mode, int frame0, int nframes,
+                                 void* dst_dev, int dst_type, int shape[4]);
 /* PoseExtractorNet::getCandidatesCopy (poseExtractorNet.cpp:246-282) of one collected frame:
  * candidates_host [parts][127][3] (x, y in output pixels = net pixels * scaleNetToOutput, score),
  * counts_host [parts]; either may be NULL. */
@@ -533,6 +548,9 @@ int opk_hand_detect(int pose_model, const float* keypoints_host, int people, int
 typedef struct opk_extractor opk_extractor;
 #define OPK_EXTRACT_FACE 0
 #define OPK_EXTRACT_HAND 1
+/* A host-only context may create an extractor (and attach it to a pose extractor, for the
+ * argument and state checks); it used to be refused here with OPK_ERR_ARG, now
+ * opk_extractor_forward is what needs a device context (OPK_ERR_ARG there). */
 int opk_extractor_create(opk_ctx* ctx, opk_net* net, int kind, int net_w, int net_h,
                          opk_extractor** out);
 int opk_extractor_destroy(opk_extractor* ex);
@@ -564,6 +582,46 @@ int opk_extractor_forward(opk_extractor* ex, const uint8_t* frames_dev, int nfra
  * inverse map (frame <- crop) and the crop's net input [3][net_h][net_w] on device */
 int opk_extractor_crop_count(opk_extractor* ex);
 int opk_extractor_crop(opk_extractor* ex, int i, double* matrix_host, const float** input_dev);
+
+/* ---- Face / hand stages inside the pose pipeline (the reference's --face --hand wiring:
+ * WFaceDetector + WFaceExtractorNet and WHandDetector + WHandExtractorNet behind WPoseExtractor,
+ * wrapperAuxiliary.hpp).  At most one face and one hand extractor per pose extractor.  The
+ * extractor must be of the pose extractor's context and its net must not be the pose net
+ * (OPK_ERR_ARG); the pose model must have the detector's body parts (OPK_ERR_UNSUPPORTED, as
+ * opk_face_detect); a second extractor of a kind, and attaching or detaching with batches in
+ * flight, are OPK_ERR_STATE.  An extractor destroyed while attached counts as detached from then on.
+ * While one is attached the pipeline accepts the raw-frame path only (opk_pose_submit_frames,
+ * opk_pose_forward_frames): every other submit / forward fails with OPK_ERR_STATE, because face /
+ * hand extraction needs the frames.  opk_pose_collect then, after the host assembly of batch i,
+ * builds each frame's rectangles from the batch's keypoints (opk_face_detect / opk_hand_detect of
+ * what opk_pose_keypoints returns), concatenates them in frame order and runs the attached
+ * extractors on batch i's frames, on the context stream -- behind the nets of batch i + 1 that an
+ * earlier submit queued, so the device stays busy during assembly and table building.
+ * Frame lifetime (beside the stream contract of opk_pose_submit): THE FRAME BUFFER OF A SUBMITTED
+ * BATCH MUST STAY UNCHANGED UNTIL THAT BATCH IS COLLECTED.
+ * The stage warps each net batch's crops right before its forward, so it holds at most max_batch
+ * crops of net input whatever the number of people and frames (same kernel, tables and stream
+ * order as opk_extractor_forward: the same values); after a stage run opk_extractor_crop returns
+ * the matrix and a NULL input pointer. */
+int opk_pose_attach_extractor(opk_pose* pose, opk_extractor* ex);
+int opk_pose_detach_extractor(opk_pose* pose, int kind);   /* OPK_EXTRACT_* */
+/* Results of the last collected batch, person order that of opk_pose_keypoints(frame):
+ * rects_host face [people][4], hand [people][2 (left, right)][4]; keypoints_host face
+ * [people'][70][3], hand [2][people'][21][3] (left hands first), people' = min(people, max_people);
+ * zeros where the reference skips the rectangle.  OPK_ERR_STATE when no such extractor is attached
+ * or nothing is collected since. */
+int opk_pose_part_rectangles(opk_pose* pose, int kind, int frame, float* rects_host);
+int opk_pose_part_keypoints(opk_pose* pose, int kind, int frame, float* keypoints_host,
+                            int max_people);
+/* Stage timing (measurement hook, modelled on opk_pose_read_collect_times): since the last read,
+ * the collects that ran the stage, the crops they ran, the host milliseconds spent on rectangles,
+ * crop validity and tables, and the milliseconds spent where the host can block on the device:
+ * from the table upload (a copy that waits for the work queued ahead on the stream) through the
+ * enqueue of every net batch (launches wait for room in the queue) to the end of the final
+ * synchronisation.  host_ms + wait_ms is the stage's wall time but for the keypoint mapping.
+ * Pointers may be NULL. */
+int opk_pose_read_part_times(opk_pose* pose, int kind, int* batches, int* crops, double* host_ms,
+                             double* wait_ms);
 
 /* ---- Measured ceilings (no reference counterpart; SURVEY.md §8d "confirm the vendor peaks"):
  *      dense fp16 MFMA rate of v_mfma_f32_16x16x32_f16 from registers (the conv kernels'
@@ -684,6 +742,18 @@ int opk_pose_render_frames(opk_pose* pose, uint8_t* dst_dev, size_t dst_step, in
                            const uint8_t* frames_dev, int n, int width, int height, size_t step,
                            double scale_input_to_output, float render_threshold, float alpha,
                            int googly_eyes, int blend_original, int cast);
+/* opk_pose_render_frames with the face / hand stages' results (opk_pose_attach_extractor): the
+ * collected batch as one POSE layer, then one FACE layer and one HAND layer, each only if its
+ * extractor is attached, through opk_render_frames -- the bytes are opk_render_frames' for those
+ * layers.  A frame's HAND layer holds the left hands of its people in person order, then the right
+ * hands (opk_pose_part_keypoints' layout), its FACE layer one face per person; x and y of every
+ * layer are multiplied by scale_input_to_output in float. */
+int opk_pose_render_frames_parts(opk_pose* pose, uint8_t* dst_dev, size_t dst_step, int out_w,
+                                 int out_h, const uint8_t* frames_dev, int n, int width, int height,
+                                 size_t step, double scale_input_to_output, float render_threshold,
+                                 float alpha, int googly_eyes, int blend_original, int cast,
+                                 float face_threshold, float face_alpha, float hand_threshold,
+                                 float hand_alpha);
 
 /* The heat layer of opk_render_frames_heat: what one of opk_render_pose_heat_map / _heat_maps /
  * _paf / _pafs / _distance would draw on each frame, from frame f's own stack of heat_dev. */

@@ -105,6 +105,7 @@ _SIGS = {
     "opk_net_set_timing": (_i, [_p, _i]),
     "opk_net_read_timing": (_i, [_p, _ip, _c.POINTER(_d)]),
     "opk_pose_heatmaps_copy": (_i, [_p, _i, _i, _p, _ip]),
+    "opk_pose_heatmaps_copy_range": (_i, [_p, _i, _i, _i, _i, _p, _i, _ip]),
     "opk_pose_candidates": (_i, [_p, _i, _p, _ip]),
     "opk_scale_keypoints": (_i, [_p, _i, _i, _i, _d, _d, _i, _i]),
     "opk_keep_top_n_people": (_i, [_p, _i, _i, _p, _i, _p, _p, _ip]),
@@ -122,6 +123,13 @@ _SIGS = {
     "opk_extractor_forward": (_i, [_p, _p, _i, _i, _i, _c.c_size_t, _p, _p, _i, _p]),
     "opk_extractor_crop_count": (_i, [_p]),
     "opk_extractor_crop": (_i, [_p, _i, _p, _c.POINTER(_p)]),
+    "opk_pose_attach_extractor": (_i, [_p, _p]),
+    "opk_pose_detach_extractor": (_i, [_p, _i]),
+    "opk_pose_part_rectangles": (_i, [_p, _i, _i, _p]),
+    "opk_pose_part_keypoints": (_i, [_p, _i, _i, _p, _i]),
+    "opk_pose_read_part_times": (_i, [_p, _i, _ip, _ip, _c.POINTER(_d), _c.POINTER(_d)]),
+    "opk_pose_render_frames_parts": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _i, _i, _i, _c.c_size_t,
+                                          _d, _f, _f, _i, _i, _i, _f, _f, _f, _f]),
     "opk_scale_and_size": (_i, [_i, _i, _i, _i, _f, _i, _d, _c.POINTER(_d), _ip]),
     "opk_cvmat_to_input": (_i, [_p, _p, _p, _i, _i, _i, _c.c_size_t, _d, _i, _i, _i]),
     "opk_pose_set_input": (_i, [_p, _i, _i, _f, _i, _d]),

@@ -695,11 +695,79 @@ class PoseExtractor:
         _LIVE["pose"].add(self)
         self.net = net
         self.parts = pose_model_info(pose_model)["parts"]
+        self.pose_model = pose_model
+        self._attached = {}   # kind -> KeypointExtractor (kept alive while attached)
 
     def close(self):
         if self.h:
             self.L.opk_pose_destroy(self.h)
             self.h = None
+            self._attached = {}
+
+    # ---- face / hand stages (opk_pose_attach_extractor) ---------------------------------------
+    def attach(self, face=None, hands=None):
+        """Run these KeypointExtractors (kind FACE / HAND) inside collect(): rectangles from each
+        frame's pose keypoints, then the extractor on the batch's frames.  Only forward_frames /
+        submit_frames are accepted while one is attached, and a submitted batch's frames must stay
+        unchanged until it is collected."""
+        for ex, kind in ((face, FACE), (hands, HAND)):
+            if ex is None:
+                continue
+            if ex.kind != kind:
+                raise ValueError("face wants a FACE extractor, hands a HAND extractor")
+            check(self.L.opk_pose_attach_extractor(self.h, ex.h))
+            self._attached[kind] = ex
+
+    def detach(self, kind):
+        check(self.L.opk_pose_detach_extractor(self.h, kind))
+        self._attached.pop(kind, None)
+
+    def _part_rectangles(self, kind, frame):
+        n = max(self.num_people(frame), 0)
+        out = np.zeros((n, 2 if kind == HAND else 1, 4), np.float32)
+        check(self.L.opk_pose_part_rectangles(self.h, kind, frame,
+                                              out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def _part_keypoints(self, kind, frame):
+        n = max(self.num_people(frame), 0)
+        parts = self._attached[kind].parts if kind in self._attached else (21 if kind == HAND else 70)
+        out = np.zeros((2 if kind == HAND else 1, n, parts, 3), np.float32)
+        check(self.L.opk_pose_part_keypoints(self.h, kind, frame,
+                                             out.ctypes.data_as(ctypes.c_void_p), n))
+        return out
+
+    def face_rectangles(self, frame):
+        """[people, 4] (x, y, width, height) of a collected frame, person order of keypoints()."""
+        return self._part_rectangles(FACE, frame)[:, 0]
+
+    def hand_rectangles(self, frame):
+        """[people, 2 (left, right), 4]."""
+        return self._part_rectangles(HAND, frame)
+
+    def face_keypoints(self, frame):
+        """[people, 70, 3]; zeros where the reference skips the rectangle."""
+        return self._part_keypoints(FACE, frame)[0]
+
+    def hand_keypoints(self, frame):
+        """[2 (left, right), people, 21, 3]."""
+        return self._part_keypoints(HAND, frame)
+
+    def datum(self, frame):
+        """datum_keypoint_vector of a collected frame: pose and, for the attached extractors, face
+        and both hands -- ready for people_json / save_people_json."""
+        face = self.face_keypoints(frame) if FACE in self._attached else None
+        hands = tuple(self.hand_keypoints(frame)) if HAND in self._attached else (None, None)
+        return datum_keypoint_vector(self.keypoints(frame)[0], face, hands)
+
+    def read_part_times(self, kind):
+        """{batches, crops, host_ms, wait_ms} of the stage since the last read: host time for
+        rectangles, crop validity and tables; time waiting for the device."""
+        b, c = ctypes.c_int(0), ctypes.c_int(0)
+        h, w = ctypes.c_double(0), ctypes.c_double(0)
+        check(self.L.opk_pose_read_part_times(self.h, kind, ctypes.byref(b), ctypes.byref(c),
+                                              ctypes.byref(h), ctypes.byref(w)))
+        return {"batches": b.value, "crops": c.value, "host_ms": h.value, "wait_ms": w.value}
 
     def __del__(self):
         try:
@@ -822,17 +890,53 @@ class PoseExtractor:
 
     def render_frames(self, frames, scale=1.0, out_size=None, threshold=0.05, alpha=0.6,
                       googly_eyes=False, blend_original=True, cast=CAST_CPU, out=None, element=0,
-                      alpha_heatmap=0.7):
+                      alpha_heatmap=0.7, face=False, hands=False, face_threshold=0.4,
+                      face_alpha=0.6, hand_threshold=0.2, hand_alpha=0.6):
         """The last collected batch drawn on its frames [n, h, w, 3] uint8 BGR (CUDA) ->
         uint8 [n, out_h, out_w, 3]; keypoints are scaled by `scale` (scaleInputToOutput).
         element (--part_to_show, see render_element): 0 the keypoints; any other draws that heat
         map / PAF of the batch instead, evaluated from the net output (no full-resolution stack
-        is written), blended with alpha_heatmap."""
+        is written), blended with alpha_heatmap.
+        face / hands: also draw the attached extractors' results (attach) as a FACE and a HAND
+        layer after the POSE layer (opk_pose_render_frames_parts when the flags name every attached
+        extractor; a subset is put together from the accessors and drawn by Context.render_frames,
+        the same bytes)."""
         n, h, w, c = frames.shape
         assert c == 3 and frames.dtype == torch.uint8
         ow, oh = out_size if out_size is not None else (w, h)
         if out is None:
             out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
+        if face or hands:
+            if element != 0:
+                raise ValueError("face / hand layers are drawn with the keypoints (element 0)")
+            if (face and FACE not in self._attached) or (hands and HAND not in self._attached):
+                raise ValueError("no such extractor attached")
+            if bool(face) == (FACE in self._attached) and bool(hands) == (HAND in self._attached):
+                check(self.L.opk_pose_render_frames_parts(   # every attached extractor's layer
+                    self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh, _ptr(frames), n, w, h,
+                    w * 3, float(scale), threshold, alpha, int(googly_eyes), int(blend_original),
+                    cast, face_threshold, face_alpha, hand_threshold, hand_alpha))
+                return out
+            # a subset of the attached extractors: the same layers, put together here
+            s = np.float32(scale)
+
+            def layer(kind, arrays, per, th, al, **kw):
+                kp = np.concatenate(arrays).astype(np.float32)
+                kp[..., :2] *= s   # scaleKeypoints: x and y times scaleInputToOutput, in float
+                dev = torch.from_numpy(np.ascontiguousarray(kp)).to(frames.device) if kp.size else None
+                return RenderLayer(kind, dev, [per * c for c in counts], th, al, **kw)
+
+            counts = [self.num_people(f) for f in range(n)]
+            layers = [layer(LAYER_POSE, [self.keypoints(f)[0] for f in range(n)], 1, threshold,
+                            alpha, pose_model=self.pose_model, googly_eyes=googly_eyes)]
+            if face:
+                layers.append(layer(LAYER_FACE, [self.face_keypoints(f) for f in range(n)], 1,
+                                    face_threshold, face_alpha))
+            if hands:   # a frame's left hands, then its right hands
+                parts = self._attached[HAND].parts
+                layers.append(layer(LAYER_HAND, [self.hand_keypoints(f).reshape(-1, parts, 3)
+                                                 for f in range(n)], 2, hand_threshold, hand_alpha))
+            return self.ctx.render_frames(frames, layers, scale, out_size, blend_original, cast, out)
         check(self.L.opk_pose_render_frames_element(
             self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh, _ptr(frames), n, w, h, w * 3,
             float(scale), int(element), threshold, alpha, alpha_heatmap, int(googly_eyes),
@@ -892,6 +996,25 @@ class PoseExtractor:
         dev = torch.empty(tuple(shape), dtype=torch.float32, device="cuda")
         check(self.L.opk_pose_heatmaps_copy(self.h, types, scale_mode, _ptr(dev), shape))
         return dev.cpu().numpy()
+
+    def heatmaps_copy_range(self, types=7, scale_mode=8, frames=None, dtype=torch.float32, out=None):
+        """heatmaps_copy's values for frames = (first, count) of the last batch (None: all), as a
+        CUDA tensor [count, channels, H, W], written straight from the net output: the
+        full-resolution stack is never materialised (opk_pose_heatmaps_copy_range).  dtype
+        torch.float32, or torch.uint8 with scale_mode 7 (UnsignedChar): min(value, 255)."""
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError("heat maps are float32 or uint8")
+        f0, nf = (0, -1) if frames is None else (int(frames[0]), int(frames[1]))
+        kind = 0 if dtype == torch.float32 else 2   # OPK_F32 / OPK_U8
+        shape = (ctypes.c_int * 4)()
+        check(self.L.opk_pose_heatmaps_copy_range(self.h, types, scale_mode, f0, nf, None, kind,
+                                                  shape))
+        if out is None:
+            out = torch.empty(tuple(shape), dtype=dtype, device="cuda")
+        assert out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.is_contiguous()
+        check(self.L.opk_pose_heatmaps_copy_range(self.h, types, scale_mode, f0, nf, _ptr(out),
+                                                  kind, shape))
+        return out
 
     def candidates(self, frame):
         """getCandidatesCopy: list over parts of [count, 3] arrays (x, y output pixels, score)."""
@@ -1011,8 +1134,10 @@ class KeypointExtractor:
             p = ctypes.c_void_p()
             check(self.L.opk_extractor_crop(self.h, i, m.ctypes.data_as(ctypes.c_void_p),
                                             ctypes.byref(p)))
-            x = np.empty((3, h, w), np.float32)
-            check(self.L.opk_memcpy_d2h(self.ctx.h, x.ctypes.data_as(ctypes.c_void_p), p,
-                                        x.nbytes))
+            x = None   # after a pose-pipeline stage run: the inputs are staged per net batch
+            if p.value:
+                x = np.empty((3, h, w), np.float32)
+                check(self.L.opk_memcpy_d2h(self.ctx.h, x.ctypes.data_as(ctypes.c_void_p), p,
+                                            x.nbytes))
             out.append((m.reshape(2, 3), x))
         return out

@@ -617,6 +617,15 @@ int opk_pose_heatmaps_copy(opk_pose* p, int types, int scale_mode, float* dst_de
     });
 }
 
+int opk_pose_heatmaps_copy_range(opk_pose* p, int types, int scale_mode, int frame0, int nframes,
+                                 void* dst_dev, int dst_type, int shape[4])
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p && shape, "NULL argument");
+        p->pose->heatmaps_copy_range(types, scale_mode, frame0, nframes, dst_dev, dst_type, shape);
+    });
+}
+
 int opk_pose_candidates(opk_pose* p, int frame, float* candidates_host, int* counts_host)
 {
     return guarded_net([&] {
@@ -659,7 +668,7 @@ int opk_extractor_create(opk_ctx* ctx, opk_net* net, int kind, int net_w, int ne
 {
     return guarded_net([&] {
         OPK_CHECK_ARG(ctx && net && out, "NULL argument");
-        OPK_CHECK_ARG(ctx->device >= 0, "extraction needs a device context");
+        // (a host-only context can create and attach one; opk_extractor_forward needs a device)
         *out = new opk_extractor{
             ctx, std::make_unique<opk::KeypointExtractor>(ctx, net->net.get(), kind, net_w, net_h)};
     });
@@ -726,8 +735,139 @@ int opk_extractor_crop(opk_extractor* ex, int i, double* matrix, const float** i
         if (matrix) std::memcpy(matrix, k->crop_matrix(i), 6 * sizeof(double));
         if (input_dev) {
             // crops are laid out [crops][3][net_h][net_w]
-            *input_dev = k->crop_inputs() + (size_t)i * 3 * k->net_w() * k->net_h();
+            // (NULL after a pipeline-stage run: only one net batch's crops are ever staged)
+            const float* in = k->crop_inputs();
+            *input_dev = in ? in + (size_t)i * 3 * k->net_w() * k->net_h() : nullptr;
         }
+    });
+}
+
+// ---- face / hand stages of the pose pipeline ---------------------------------------------------
+int opk_pose_attach_extractor(opk_pose* p, opk_extractor* ex)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p && ex, "NULL argument");
+        p->pose->attach_extractor(ex->ex.get());
+    });
+}
+
+int opk_pose_detach_extractor(opk_pose* p, int kind)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        p->pose->detach_extractor(kind);
+    });
+}
+
+int opk_pose_part_rectangles(opk_pose* p, int kind, int frame, float* rects_host)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        const opk::Rect* r = p->pose->part_rectangles(kind, frame);
+        const size_t count = (size_t)p->pose->num_people(frame) * (kind == OPK_EXTRACT_HAND ? 2 : 1);
+        OPK_CHECK_ARG(count == 0 || rects_host, "NULL rectangles");
+        if (count) std::memcpy(rects_host, r, count * sizeof(opk::Rect));
+    });
+}
+
+int opk_pose_part_keypoints(opk_pose* p, int kind, int frame, float* keypoints_host, int max_people)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        int first = 0, total = 0, parts = 0;
+        const float* kp = p->pose->part_keypoints(kind, frame, &first, &total, &parts);
+        const int people = std::min(max_people, p->pose->num_people(frame));
+        if (people <= 0) return;
+        OPK_CHECK_ARG(keypoints_host, "NULL keypoints");
+        const size_t person = (size_t)parts * 3;
+        for (int hd = 0; hd < (kind == OPK_EXTRACT_HAND ? 2 : 1); ++hd)
+            std::memcpy(keypoints_host + (size_t)hd * people * person,
+                        kp + ((size_t)hd * total + first) * person, people * person * sizeof(float));
+    });
+}
+
+int opk_pose_read_part_times(opk_pose* p, int kind, int* batches, int* crops, double* host_ms,
+                             double* wait_ms)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        p->pose->read_part_times(kind, batches, crops, host_ms, wait_ms);
+    });
+}
+
+int opk_pose_render_frames_parts(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w, int out_h,
+                                 const uint8_t* frames, int n, int width, int height, size_t step,
+                                 double scale, float threshold, float alpha, int googly_eyes,
+                                 int blend_original, int cast, float face_threshold,
+                                 float face_alpha, float hand_threshold, float hand_alpha)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        opk::PoseHip& pose = *p->pose;
+        if (pose.frames() == 0) throw opk::Error(OPK_ERR_STATE, "no collected batch to render");
+        if (n != pose.frames())
+            throw opk::Error(OPK_ERR_STATE, "the collected batch has " +
+                                                std::to_string(pose.frames()) + " frames, not " +
+                                                std::to_string(n));
+        const float s = (float)scale;   // scaleKeypoints: x and y times scaleInputToOutput, in float
+        auto scaled = [s](std::vector<float>& kp) {
+            if (s != 1.f)
+                for (size_t i = 0; i < kp.size(); i += 3) {
+                    kp[i] *= s;
+                    kp[i + 1] *= s;
+                }
+        };
+        const int parts = opk::pose_model(pose.model()).parts;
+        std::vector<int> counts[3];
+        std::vector<float> kp[3];
+        opk_render_layer layers[3] = {};
+        int nl = 0;
+        for (int f = 0; f < n; ++f) {
+            const int people = pose.num_people(f);
+            counts[0].push_back(people);
+            const auto& k = pose.keypoints(f);
+            kp[0].insert(kp[0].end(), k.begin(), k.begin() + (size_t)people * parts * 3);
+        }
+        scaled(kp[0]);
+        layers[nl].kind = OPK_LAYER_POSE;
+        layers[nl].pose_model = pose.model();
+        layers[nl].counts_host = counts[0].data();
+        layers[nl].render_threshold = threshold;
+        layers[nl].alpha = alpha;
+        layers[nl].googly_eyes = googly_eyes;
+        ++nl;
+        p->ctx->bind();
+        for (int kind = 0; kind < 2; ++kind) {
+            if (!pose.attached(kind)) continue;
+            const int hands = kind == OPK_EXTRACT_HAND ? 2 : 1;
+            std::vector<float>& v = kp[1 + kind];
+            for (int f = 0; f < n; ++f) {   // a frame's left hands, then its right hands
+                int first = 0, total = 0, P = 0;
+                const float* src = pose.part_keypoints(kind, f, &first, &total, &P);
+                const int people = pose.num_people(f);
+                counts[1 + kind].push_back(hands * people);
+                for (int hd = 0; hd < hands; ++hd) {
+                    const float* q = src + ((size_t)hd * total + first) * P * 3;
+                    v.insert(v.end(), q, q + (size_t)people * P * 3);
+                }
+            }
+            scaled(v);
+            float* dev = static_cast<float*>(
+                pose.part_render_scratch(kind, std::max<size_t>(1, v.size()) * sizeof(float)));
+            if (!v.empty()) {
+                OPK_HIP(hipMemcpyAsync(dev, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice,
+                                       p->ctx->stream));
+                OPK_HIP(hipStreamSynchronize(p->ctx->stream));   // `v` is pageable
+            }
+            layers[nl].kind = kind == OPK_EXTRACT_HAND ? OPK_LAYER_HAND : OPK_LAYER_FACE;
+            layers[nl].keypoints_dev = dev;
+            layers[nl].counts_host = counts[1 + kind].data();
+            layers[nl].render_threshold = kind == OPK_EXTRACT_HAND ? hand_threshold : face_threshold;
+            layers[nl].alpha = kind == OPK_EXTRACT_HAND ? hand_alpha : face_alpha;
+            ++nl;
+        }
+        opk::render_frames(p->ctx, dst, dst_step, out_w, out_h, frames, n, width, height, step,
+                           scale, layers, nl, blend_original, cast, kp[0].data(), kp[0].size());
     });
 }
 

@@ -4,6 +4,7 @@
 #include "extract.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -200,8 +201,11 @@ const float* KeypointExtractor::heatmaps(int shape[5]) const
 
 void KeypointExtractor::extract(const uint8_t* frames, int nframes, int w, int h, size_t step,
                                 const Rect* rects, const int* frame_of, int people,
-                                float* keypoints)
+                                float* keypoints, bool chunked)
 {
+    const auto t_start = std::chrono::steady_clock::now();
+    host_ms_ = wait_ms_ = 0.;
+    OPK_CHECK_ARG(ctx_->device >= 0, "extraction needs a device context");
     OPK_CHECK_ARG(people >= 0, "negative people");
     OPK_CHECK_ARG(nframes > 0 && w > 0 && h > 0, "Empty cvInputData.");
     OPK_CHECK_ARG(frames, "NULL frames");
@@ -262,7 +266,8 @@ void KeypointExtractor::extract(const uint8_t* frames, int nframes, int w, int h
     ctx_->bind();
     hipStream_t s = ctx_->stream;
 
-    // 2. every crop warped in one launch: per-crop separable tap tables + source frame index
+    // 2. per-crop separable tap tables + source frame index, uploaded whole; the crops are warped
+    //    in one launch (or, chunked, one launch per net batch in step 3)
     const int tw = net_w_ + net_h_;   // {tap, fraction} entries per crop
     std::vector<int> host((size_t)n * tw * 2 + n);
     for (int i = 0; i < n; ++i) {
@@ -270,13 +275,25 @@ void KeypointExtractor::extract(const uint8_t* frames, int nframes, int w, int h
         crop_axis_tables(crop_matrix(i), net_w_, net_h_, t, t + 2 * net_w_);
         host[(size_t)n * tw * 2 + i] = crops[i].frame;
     }
+    // host work ends here.  Everything from the upload on can block on the device: the copy from
+    // pageable memory waits for the work queued ahead on the stream, the launches below for room
+    // in the queue, the synchronisation for the results -- all of it is wait_ms_
+    const auto t_wait = std::chrono::steady_clock::now();
+    host_ms_ = std::chrono::duration<double, std::milli>(t_wait - t_start).count();
     int* tabs = static_cast<int*>(tabs_.get(host.size() * sizeof(int)));
     OPK_HIP(hipMemcpyAsync(tabs, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, s));
     const size_t crop_elems = (size_t)3 * net_h_ * net_w_;
-    float* in = static_cast<float*>(inputs_.get((size_t)n * crop_elems * sizeof(float)));
-    launch_cvmat_to_input(in, frames, n, h, w, step, net_h_, net_w_, tabs, tabs + 2 * net_w_,
-                          ctx_->warp_weight_table(false), 2, 1, s, tabs + (size_t)n * tw * 2,
-                          tw);
+    // (chunked: at most max_batch crops of net input at once, warped before each forward below)
+    const int staged = chunked ? std::min(n, max_batch_) : n;
+    float* in = static_cast<float*>(inputs_.get((size_t)staged * crop_elems * sizeof(float)));
+    inputs_whole_ = !chunked;
+    const int* frame_tab = tabs + (size_t)n * tw * 2;
+    auto warp = [&](float* dst, int first, int count) {
+        const int* t = tabs + (size_t)first * tw * 2;
+        launch_cvmat_to_input(dst, frames, count, h, w, step, net_h_, net_w_, t, t + 2 * net_w_,
+                              ctx_->warp_weight_table(false), 2, 1, s, frame_tab + first, tw);
+    };
+    if (!chunked) warp(in, 0, n);
 
     // 3. net on batches of crops (power-of-two sizes, so at most log2(max_batch) + 1 plans),
     //    each followed by its resize x8 + per-part maximum (evaluated lazily, heat_dev.h) and, on
@@ -294,7 +311,8 @@ void KeypointExtractor::extract(const uint8_t* frames, int nframes, int w, int h
     for (int done = 0; done < n;) {
         int b = 1;
         while (b * 2 <= std::min(max_batch_, n - done)) b *= 2;
-        net_->forward(in + (size_t)done * crop_elems, b, net_h_, net_w_);
+        if (chunked) warp(in, done, b);   // (in order after the previous batch's forward read `in`)
+        net_->forward(in + (chunked ? 0 : (size_t)done * crop_elems), b, net_h_, net_w_);
         const int oh = net_->out_h(), ow = net_->out_w();
         HeatMap heat{};
         heat.channels = net_->out_channels();
@@ -320,6 +338,7 @@ void KeypointExtractor::extract(const uint8_t* frames, int nframes, int w, int h
     float* hp = static_cast<float*>(hpeaks_.get((size_t)n * P * 3 * sizeof(float)));
     OPK_HIP(hipMemcpyAsync(hp, peaks, (size_t)n * P * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
     OPK_HIP(hipStreamSynchronize(s));
+    wait_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wait).count();
 
     // 4. keypoints = M (x, y) in double, stored as float (faceExtractorCaffe.cpp:251-266,
     //    connectKeypoints handExtractorCaffe.cpp:75-99); multi-scale keeps the scale with the

@@ -4,6 +4,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "context.h"
@@ -46,8 +47,21 @@ public:
     // hand [people][2]; frame_of[people] (NULL: all frame 0).  keypoints (host): face
     // [people][parts][3], hand [2][people][parts][3] (left hands first); zeros for the rectangles
     // the reference skips.
+    // chunked (the pose pipeline's stage): each net batch's crops are warped right before its
+    // forward into a buffer of max_batch crops -- same kernel, tables and stream order, so the
+    // same values -- instead of every crop of the call before the first batch; crop_inputs() is
+    // then NULL.
     void extract(const uint8_t* frames, int nframes, int w, int h, size_t step, const Rect* rects,
-                 const int* frame_of, int people, float* keypoints);
+                 const int* frame_of, int people, float* keypoints, bool chunked = false);
+    // wall milliseconds of the last extract(): host work (crop validity, inverse maps, tables),
+    // then everything that can block on the device -- the table upload, the enqueue of every net
+    // batch (launches wait for room in the queue) and the final synchronisation
+    double last_host_ms() const { return host_ms_; }
+    double last_wait_ms() const { return wait_ms_; }
+    Context* context() const { return ctx_; }
+    NetHip* net() const { return net_; }
+    // expires when this extractor is destroyed (a pose pipeline it is attached to then drops it)
+    std::weak_ptr<void> liveness() const { return alive_; }
 
     int parts() const;
     int kind() const { return kind_; }
@@ -56,7 +70,10 @@ public:
     // the crops of the last extract(): count, net inputs ([crops][3][net_h][net_w] device) and
     // per crop the 2x3 inverse map (frame <- crop)
     int crops() const { return (int)crop_m_.size() / 6; }
-    const float* crop_inputs() const { return static_cast<const float*>(inputs_.ptr); }
+    const float* crop_inputs() const
+    {
+        return inputs_whole_ ? static_cast<const float*>(inputs_.ptr) : nullptr;
+    }
     const double* crop_matrix(int i) const { return crop_m_.data() + 6 * (size_t)i; }
 
 private:
@@ -69,6 +86,9 @@ private:
     DevBuf inputs_, tabs_, peaks_;
     HostBuf hpeaks_;
     std::vector<double> crop_m_;
+    bool inputs_whole_ = true;   // inputs_ holds every crop of the last extract()
+    double host_ms_ = 0., wait_ms_ = 0.;
+    std::shared_ptr<void> alive_ = std::make_shared<int>(0);
     int heat_mode_ = -1;
     DevBuf heat_out_, heat_slots_;
     int heat_shape_[5] = {0, 0, 0, 0, 0};

@@ -181,6 +181,44 @@ void PoseHip::heatmaps_copy(int types, int scale_mode, float* dst, int shape[4])
     OPK_HIP(hipStreamSynchronize(ctx_->stream));   // `sel` dies at return
 }
 
+void PoseHip::heatmaps_copy_range(int types, int scale_mode, int frame0, int nframes, void* dst,
+                                  int dst_type, int shape[4])
+{
+    OPK_CHECK_ARG(types > 0 && types < 8, "heat-map types: bits 0 parts, 1 background, 2 PAFs");
+    OPK_CHECK_ARG(scale_mode >= 0 && scale_mode <= 8, "unknown ScaleMode");
+    OPK_CHECK_ARG(dst_type == OPK_F32 || dst_type == OPK_U8, "heat maps are float or uint8");
+    OPK_CHECK_ARG(dst_type == OPK_F32 || scale_mode == 7,
+                  "uint8 heat maps need ScaleMode::UnsignedChar");
+    // a range no batch can hold is an argument error; whether there is a batch is a state
+    // (lazy_heat below); then the range against that batch
+    OPK_CHECK_ARG(frame0 >= 0 && (nframes > 0 || nframes == -1),
+                  "frame range outside the collected batch: frame0 >= 0, nframes > 0 or -1");
+    const HeatMap& heat = lazy_heat();   // a collected batch, no later batch in flight
+    if (nframes == -1 && frame0 < n_) nframes = n_ - frame0;   // to the batch's end
+    OPK_CHECK_ARG(nframes > 0 && frame0 <= n_ - nframes, "frame range outside the collected batch");
+    const PoseModelInfo& m = pose_model(model_);
+    HeatSelection sel{};
+    auto run = [&](int s, int src0, int count, int paf) {
+        sel.dst0[s] = sel.nsel;
+        sel.src0[s] = src0;
+        sel.count[s] = count;
+        sel.paf[s] = paf;
+        sel.nsel += count;
+    };
+    run(0, 0, (types & 1) ? m.parts : 0, 0);
+    if (types & 2)
+        OPK_CHECK_ARG(m.bkg, "You enabled `--heatmaps_add_bkg` for a model that does not contain one. "
+                             "Please, remove this flag for this model.");
+    run(1, m.parts, (types & 2) ? 1 : 0, 0);
+    run(2, m.parts + (m.bkg ? 1 : 0), (types & 4) ? 2 * m.npairs() : 0, 1);
+    shape[0] = nframes; shape[1] = sel.nsel; shape[2] = hh_; shape[3] = hw_;
+    if (!dst) return;
+    ctx_->bind();
+    launch_heat_copy_lazy(dst, dst_type == OPK_U8, heat, sel, frame0, nframes, scale_mode,
+                          ctx_->stream);
+    OPK_HIP(hipStreamSynchronize(ctx_->stream));   // as heatmaps_copy: dst is complete at return
+}
+
 void PoseHip::candidates(int frame, float* out, int* counts) const
 {
     OPK_CHECK_ARG(last_ >= 0, "no collected batch");
@@ -224,8 +262,114 @@ void PoseHip::forward_net_output(const float* net_out, int n, int oh, int ow, in
     collect();
 }
 
+void PoseHip::need_frames() const
+{
+    if (any_attached() && !cur_raw_.ptr)
+        throw Error(3, "face / hand extraction needs the frames: with an extractor attached only "
+                       "submit_frames / forward_frames are accepted");
+}
+
+void PoseHip::attach_extractor(KeypointExtractor* ex)
+{
+    OPK_CHECK_ARG(ex != nullptr, "NULL extractor");
+    OPK_CHECK_ARG(ex->context() == ctx_, "the extractor and the pose extractor must share one context");
+    OPK_CHECK_ARG(ex->net() != net_, "the extractor's net must not be the pose net");
+    const int kind = ex->kind();
+    // the detector's body parts (OPK_ERR_UNSUPPORTED as opk_face_detect / opk_hand_detect)
+    if (kind == KeypointExtractor::kFace) detect_faces(model_, nullptr, 0, 0, nullptr);
+    else detect_hands(model_, nullptr, 0, 0, nullptr);
+    if (count_ != 0) throw Error(3, "batches in flight: collect them before attaching");
+    if (attached(kind))
+        throw Error(3, std::string("a ") + (kind == KeypointExtractor::kFace ? "face" : "hand") +
+                           " extractor is already attached: detach it first");
+    part_[kind] = Part{};
+    part_[kind].ex = ex;
+    part_[kind].alive = ex->liveness();
+    part_[kind].parts = ex->parts();
+    parts_valid_ = false;
+}
+
+void PoseHip::detach_extractor(int kind)
+{
+    OPK_CHECK_ARG(kind == KeypointExtractor::kFace || kind == KeypointExtractor::kHand,
+                  "kind: face (0) or hand (1)");
+    if (count_ != 0) throw Error(3, "batches in flight: collect them before detaching");
+    part_[kind] = Part{};
+}
+
+const Rect* PoseHip::part_rectangles(int kind, int f) const
+{
+    OPK_CHECK_ARG(kind == KeypointExtractor::kFace || kind == KeypointExtractor::kHand,
+                  "kind: face (0) or hand (1)");
+    if (!attached(kind)) throw Error(3, "no such extractor attached");
+    if (!parts_valid_) throw Error(3, "no collected batch with face / hand results");
+    OPK_CHECK_ARG(f >= 0 && f < n_, "bad frame");
+    return part_[kind].rects.data() + (size_t)part_first_[f] * (kind == KeypointExtractor::kHand ? 2 : 1);
+}
+
+const float* PoseHip::part_keypoints(int kind, int f, int* first, int* total, int* parts) const
+{
+    (void)part_rectangles(kind, f);   // the same conditions
+    *first = part_first_[f];
+    *total = part_first_[n_];
+    *parts = part_[kind].parts;
+    return part_[kind].kp.data();
+}
+
+void PoseHip::read_part_times(int kind, int* batches, int* crops, double* host_ms, double* wait_ms)
+{
+    OPK_CHECK_ARG(kind == KeypointExtractor::kFace || kind == KeypointExtractor::kHand,
+                  "kind: face (0) or hand (1)");
+    Part& p = part_[kind];
+    if (!attached(kind)) throw Error(3, "no such extractor attached");
+    if (batches) *batches = p.batches;
+    if (crops) *crops = p.crops;
+    if (host_ms) *host_ms = p.host_ms;
+    if (wait_ms) *wait_ms = p.wait_ms;
+    p.batches = p.crops = 0;
+    p.host_ms = p.wait_ms = 0.;
+}
+
+void PoseHip::run_parts(const Slot& sl)
+{
+    parts_valid_ = false;
+    if (!any_attached()) return;
+    if (!sl.raw.ptr) throw Error(3, "face / hand extraction needs the frames of the collected batch");
+    const int n = sl.n;
+    const int parts = pose_model(model_).parts;
+    part_first_.assign(n + 1, 0);
+    for (int f = 0; f < n; ++f) part_first_[f + 1] = part_first_[f] + people_[f];
+    const int total = part_first_[n];
+    std::vector<int> frame_of(total);
+    for (int f = 0; f < n; ++f)
+        std::fill(frame_of.begin() + part_first_[f], frame_of.begin() + part_first_[f + 1], f);
+    for (int kind = 0; kind < 2; ++kind) {
+        Part& p = part_[kind];
+        if (!attached(kind)) continue;
+        const auto t0 = std::chrono::steady_clock::now();
+        const int per = kind == KeypointExtractor::kHand ? 2 : 1;
+        p.rects.assign((size_t)total * per, Rect{0.f, 0.f, 0.f, 0.f});
+        for (int f = 0; f < n; ++f) {
+            Rect* r = p.rects.data() + (size_t)part_first_[f] * per;
+            if (kind == KeypointExtractor::kFace) detect_faces(model_, kp_[f].data(), people_[f], parts, r);
+            else detect_hands(model_, kp_[f].data(), people_[f], parts, r);
+        }
+        p.kp.assign((size_t)per * total * p.ex->parts() * 3, 0.f);
+        const double rect_ms =
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        p.ex->extract(sl.raw.ptr, sl.raw.n, sl.raw.w, sl.raw.h, sl.raw.step, p.rects.data(),
+                      frame_of.data(), total, p.kp.data(), true);
+        ++p.batches;
+        p.crops += p.ex->crops();
+        p.host_ms += rect_ms + p.ex->last_host_ms();
+        p.wait_ms += p.ex->last_wait_ms();
+    }
+    parts_valid_ = true;
+}
+
 void PoseHip::submit(const float* frames, int n, int net_h, int net_w, int prod_w, int prod_h)
 {
+    need_frames();
     OPK_CHECK_ARG(net_ != nullptr, "no network: use forward_net_output (poseNetOutput path)");
     OPK_CHECK_ARG(count_ < 2, "two batches already in flight: collect first");
     ctx_->bind();
@@ -305,6 +449,7 @@ void PoseHip::submit_frames(const uint8_t* frames, int n, int w, int h, size_t s
     inputs_n_ = n;
     for (int i = 0; i < scale_number_; ++i) map_ratios_[i] = (float)scales[i];
     have_ratios_ = true;
+    cur_raw_ = RawFrames{frames, n, w, h, step};   // kept in the batch's slot (submit_outputs)
     try {
         if (scale_number_ == 1)
             submit(ptrs[0], n, hw[0], hw[1], w, h);
@@ -312,9 +457,11 @@ void PoseHip::submit_frames(const uint8_t* frames, int n, int w, int h, size_t s
             submit_multi(ptrs, hw, scale_number_, n, w, h);
     } catch (...) {
         have_ratios_ = false;
+        cur_raw_ = RawFrames{};
         throw;
     }
     have_ratios_ = false;
+    cur_raw_ = RawFrames{};
 }
 
 void PoseHip::forward_frames(const uint8_t* frames, int n, int w, int h, size_t step)
@@ -335,6 +482,7 @@ const float* PoseHip::net_input(int i, int* w, int* h) const
 void PoseHip::submit_multi(const float* const* frames, const int* net_hw, int nscales, int n,
                            int prod_w, int prod_h)
 {
+    need_frames();
     OPK_CHECK_ARG(net_ != nullptr, "no network: multi-scale needs the net");
     OPK_CHECK_ARG(frames && net_hw && nscales >= 1 && nscales <= kMaxResizeSources,
                   "1..8 scales");
@@ -390,6 +538,7 @@ void PoseHip::submit_multi(const float* const* frames, const int* net_hw, int ns
 void PoseHip::submit_net_output(const float* net_out, int n, int oh, int ow, int net_h,
                                 int net_w, int prod_w, int prod_h)
 {
+    need_frames();
     const NetOutput o{net_out, oh, ow};
     submit_outputs(&o, 1, n, net_h, net_w, prod_w, prod_h, false);
 }
@@ -499,6 +648,7 @@ void PoseHip::submit_outputs(const NetOutput* outs, int nscales, int n, int net_
     sl.W = W;
     sl.scale = scale;
     sl.heat = heat;
+    sl.raw = cur_raw_;
     ++count_;
 }
 
@@ -649,6 +799,7 @@ int PoseHip::collect()
     hw_ = sl.W;
     scale_net_to_output_ = sl.scale;
     heat_valid_ = false;
+    run_parts(sl);   // the attached face / hand extractors, on this batch's frames
     return n;
 }
 

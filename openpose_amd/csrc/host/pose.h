@@ -5,6 +5,7 @@
 
 #include "connector.h"
 #include "context.h"
+#include "extract.h"
 #include "net.h"
 #include "pool.h"
 
@@ -76,6 +77,11 @@ public:
     // collected batch: types bit 0 parts, bit 1 background, bit 2 PAFs (in that order), scale_mode
     // an op::ScaleMode value; dst [n][channels of the types][H][W] device (NULL: shape only)
     void heatmaps_copy(int types, int scale_mode, float* dst, int shape[4]);
+    // the same values of frames frame0 .. frame0 + nframes - 1 (nframes -1: to the batch's end)
+    // straight from the lazy map (heat_out.hip): heat_ is neither allocated nor read.  dst_type
+    // OPK_F32, or OPK_U8 (scale_mode UnsignedChar only): min(value, 255)
+    void heatmaps_copy_range(int types, int scale_mode, int frame0, int nframes, void* dst,
+                             int dst_type, int shape[4]);
     // PoseExtractorNet::getCandidatesCopy (:246-282): peaks of one frame, x/y * scaleNetToOutput;
     // out [parts][kMaxPeaks][3], counts [parts]
     void candidates(int frame, float* out, int* counts) const;
@@ -90,6 +96,34 @@ public:
     int assembly_workers() const { return pool_ ? pool_->workers() : assembly_threads(); }
     int model() const { return model_; }
 
+    // Face / hand stages (the reference's WFaceDetector + WFaceExtractorNet, WHandDetector +
+    // WHandExtractorNet workers behind WPoseExtractor): at most one extractor per kind
+    // (KeypointExtractor::kFace / kHand), of this context, over a net that is not the pose net.
+    // While one is attached only submit_frames / forward_frames are accepted, and collect() runs,
+    // after the people assembly of batch i: rectangles per frame from the batch's keypoints
+    // (detect_faces / detect_hands), concatenated in frame order, then extract(..., chunked) on
+    // batch i's frames -- queued on the context stream behind the nets of batch i + 1, which the
+    // earlier submit enqueued.  The frame buffer of a submitted batch must therefore stay
+    // unchanged until that batch is collected.
+    void attach_extractor(KeypointExtractor* ex);
+    void detach_extractor(int kind);
+    // (an extractor destroyed while attached counts as detached from then on)
+    bool attached(int kind) const
+    {
+        return kind >= 0 && kind < 2 && part_[kind].ex != nullptr && !part_[kind].alive.expired();
+    }
+    // results of the last collected batch (an OPK_ERR_STATE error without extractor or batch):
+    // rects [people] (face) or [people][2] (hand) of frame f
+    const Rect* part_rectangles(int kind, int f) const;
+    // keypoints of frame f: the whole batch's array as extract() fills it (face [total][P][3],
+    // hand [2][total][P][3]), the frame's first person in it and the batch's people
+    const float* part_keypoints(int kind, int f, int* first, int* total, int* parts) const;
+    // since the last read: batches and crops run, host ms for rectangles, crop validity and
+    // tables, ms waiting for the device
+    void read_part_times(int kind, int* batches, int* crops, double* host_ms, double* wait_ms);
+    // device scratch of the face / hand layers of a batch render (grows, never shrinks)
+    void* part_render_scratch(int kind, size_t bytes) { return part_dev_[kind & 1].get(bytes); }
+
     static constexpr int kMaxPeaks = kPoseMaxPeople;   // peaks blob [parts][128][3]
     static constexpr int kRecordHead = 16384;          // record floats copied eagerly per frame
     // host threads assembling a batch's people: at most this many, and at most the CPUs of the
@@ -98,6 +132,11 @@ public:
     static int assembly_threads();
 
 private:
+    struct RawFrames {
+        const uint8_t* ptr = nullptr;
+        int n = 0, w = 0, h = 0;
+        size_t step = 0;
+    };
     struct Slot {
         DevBuf peaks, records;
         HostBuf hpeaks, hrecords;
@@ -105,7 +144,25 @@ private:
         int n = 0, H = 0, W = 0;
         float scale = 1.f;
         HeatMap heat{};
+        RawFrames raw{};   // the batch's frames (submit_frames), for the face / hand stages
     };
+    struct Part {
+        KeypointExtractor* ex = nullptr;
+        std::weak_ptr<void> alive;    // KeypointExtractor::liveness
+        int parts = 0;
+        std::vector<Rect> rects;      // the collected batch's, frame after frame
+        std::vector<float> kp;        // as extract() fills it
+        int batches = 0, crops = 0;
+        double host_ms = 0., wait_ms = 0.;
+    };
+    Part part_[2];
+    DevBuf part_dev_[2];
+    std::vector<int> part_first_;     // [n + 1]: first person of each frame in the batch's arrays
+    bool parts_valid_ = false;
+    RawFrames cur_raw_{};             // set by submit_frames for the submit it makes
+    bool any_attached() const { return attached(0) || attached(1); }
+    void need_frames() const;         // the OPK_ERR_STATE of a submit without frames
+    void run_parts(const Slot& sl);
     struct NetOutput {
         const float* ptr;
         int h, w;

@@ -215,4 +215,17 @@ void launch_f32_to_f64(double* dst, const float* src, size_t n, hipStream_t stre
 void launch_heat_copy(float* dst, const float* heat, const int* sel_dev, int nsel, int frames,
                       int channels, size_t hw, int scale_mode, hipStream_t stream);
 
+// ---- getHeatMapsCopy from the lazy map (heat_out.hip) -----------------------------------------
+// The destination channels as up to three runs (parts, background, PAFs): run s = destination
+// channels dst0[s] .. dst0[s] + count[s] - 1 from source channels src0[s] .., PAF scaling if paf[s]
+struct HeatSelection {
+    int nsel;
+    int dst0[3], src0[3], count[3], paf[3];
+};
+// dst [nframes][sel.nsel][M.h][M.w] (float, or uint8 with ScaleMode::UnsignedChar: min(v, 255)) =
+// launch_heat_copy of frames frame0 .. of the lazy map M's resize / merge, bit for bit, without
+// the materialised stack
+void launch_heat_copy_lazy(void* dst, bool u8, const HeatMap& M, const HeatSelection& sel,
+                           int frame0, int nframes, int scale_mode, hipStream_t stream);
+
 }  // namespace opk
