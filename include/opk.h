@@ -137,6 +137,22 @@ int opk_paf_scores(opk_ctx* ctx, float* pair_scores_dev, const float* heat_dev,
                    int heat_h, int heat_w, int max_peaks, float inter_threshold,
                    float inter_min_above_threshold, float default_nms_threshold);
 
+/* The same scores on the lazy heat map the pipeline scores (opk_pose_*: the merged map is never
+ * written; every sample is resized from the net outputs), built from `num_sources` net outputs
+ * (source_sizes: {N, C, h, w} each) at target_h x target_w with heat-map `semantics`
+ * (scale_ratios: as opk_resize_and_merge_semantics).  rec_floats 0: out_dev is the dense
+ * [N][numPairs][maxPeaks][maxPeaks] array of opk_paf_scores.  rec_floats > 1: out_dev holds one
+ * record of rec_floats floats per frame, as the pipeline's: [0] = the number of scores (-1 when
+ * they do not fit, nothing else written), then the nA x nB scores of pair 0, pair 1, ...
+ * *staged_bytes (may be NULL): the bytes of a workgroup's on-chip copy of the sources, 0 when the
+ * kernels read them from memory. */
+int opk_paf_scores_sources(opk_ctx* ctx, float* out_dev, int rec_floats,
+                           const float* const* sources_dev, int num_sources,
+                           const int* source_sizes, int target_h, int target_w, int semantics,
+                           const float* scale_ratios, const float* peaks_dev, int pose_model,
+                           int max_peaks, float inter_threshold, float inter_min_above_threshold,
+                           float default_nms_threshold, size_t* staged_bytes);
+
 /* ---- connectBodyParts: replaces op::connectBodyPartsGpu<float>
  *      (include/openpose/net/bodyPartConnectorBase.hpp:17-24) with connectBodyPartsCpu semantics
  *      (bodyPartConnectorBase.cpp:1327-1377): GPU pair scores + host people assembly.
@@ -370,6 +386,13 @@ int opk_net_blob_planes(opk_net* net, const char* name, int frame0, int nframes,
  * "<layer>\t<kernel instantiation>\n" line per launch.  *needed = bytes incl. the NUL; the text
  * is copied when size >= *needed. */
 int opk_net_launch_log(opk_net* net, char* buf, size_t size, size_t* needed);
+/* The same log outside a net forward (tests: which route a launcher took).  _begin attaches an
+ * empty log owned by the library to the calling thread; every launch that thread makes until _end
+ * adds its line (the layer is empty outside a forward; a forward run with LAUNCH_LOG 1 logs to the
+ * net's own log and hands this one back afterwards).  _end detaches it and returns its lines with
+ * the buffer convention above; it may be called again to fetch the text. */
+int opk_launch_log_begin(void);
+int opk_launch_log_end(char* buf, size_t size, size_t* needed);
 
 /* ---- Pose extractor: replaces op::PoseExtractorCaffe::forwardPass
  *      (src/openpose/pose/poseExtractorCaffe.cpp:200-334) for a batch of frames:

@@ -50,6 +50,8 @@ _SIGS = {
     "opk_pose_set_map_semantics": (_i, [_p, _i]),
     "opk_resize_and_merge_semantics": (_i, [_p, _p, _c.POINTER(_p), _i, _ip, _ip, _fp, _i]),
     "opk_paf_scores": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _f]),
+    "opk_paf_scores_sources": (_i, [_p, _p, _i, _c.POINTER(_p), _i, _ip, _i, _i, _i, _fp, _p, _i, _i,
+                                    _f, _f, _f, _c.POINTER(_c.c_size_t)]),
     "opk_connect_body_parts": (_i, [_p, _p, _p, _i, _ip, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i,
                                     _f, _f, _f, _i]),
     "opk_assemble_people": (_i, [_p, _p, _i, _ip, _p, _p, _i, _i, _i, _f, _f, _i]),
@@ -68,6 +70,8 @@ _SIGS = {
     "opk_net_output": (_i, [_p, _c.POINTER(_p), _ip]),
     "opk_net_blob": (_i, [_p, _c.c_char_p, _i, _i, _p, _ip]),
     "opk_net_launch_log": (_i, [_p, _c.c_char_p, _c.c_size_t, _c.POINTER(_c.c_size_t)]),
+    "opk_launch_log_begin": (_i, []),
+    "opk_launch_log_end": (_i, [_c.c_char_p, _c.c_size_t, _c.POINTER(_c.c_size_t)]),
     "opk_pose_create": (_i, [_p, _p, _i, _c.POINTER(_p)]),
     "opk_pose_create_model": (_i, [_p, _p, _i, _i, _i, _c.POINTER(_p)]),
     "opk_pose_destroy": (_i, [_p]),

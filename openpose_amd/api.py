@@ -69,6 +69,17 @@ def _row_bytes(t, n, h, w):
     return step
 
 
+def _frame_rows(t, width=None):
+    """(n, h, w, row bytes) of a uint8 frame batch: [n, h, w, 3], or [n, h, row bytes] with padded
+    rows of `width` pixels (the source side of _row_bytes)."""
+    assert t.dtype == torch.uint8 and t.dim() in (3, 4)
+    if t.dim() == 4:
+        assert t.shape[3] == 3 and width in (None, t.shape[2])
+        return t.shape[0], t.shape[1], t.shape[2], t.shape[2] * 3
+    assert width is not None and t.shape[2] >= width * 3, "padded rows need the frame width"
+    return t.shape[0], t.shape[1], width, t.shape[2]
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -109,6 +120,26 @@ class dev_switches:
         L = _lib.load()
         for k in self.kv:
             L.opk_dev_set(k.encode(), 0, 1)
+        return False
+
+
+class launch_log:
+    """Context manager over opk_launch_log_begin / _end: the [(layer, kernel)] list of every launch
+    this thread makes inside the block, e.g. `with launch_log() as log: ...; [k for _, k in log]`
+    (filled on exit; the layer is empty outside a net forward)."""
+
+    def __enter__(self):
+        self.lines = []
+        check(_lib.load().opk_launch_log_begin())
+        return self.lines
+
+    def __exit__(self, *exc):
+        L = _lib.load()
+        need = ctypes.c_size_t()
+        check(L.opk_launch_log_end(None, 0, ctypes.byref(need)))
+        buf = ctypes.create_string_buffer(need.value)
+        check(L.opk_launch_log_end(buf, need.value, ctypes.byref(need)))
+        self.lines.extend(tuple(line.split("\t", 1)) for line in buf.value.decode().splitlines())
         return False
 
 
@@ -173,13 +204,14 @@ class Context:
         check(self.L.opk_resize_and_merge_semantics(self.h, _ptr(target), ptrs, n,
                                                     int4(target.shape), sizes, ratios, semantics))
 
-    def cvmat_to_input(self, net_input, frames, scale, normalize=1):
+    def cvmat_to_input(self, net_input, frames, scale, normalize=1, width=None):
         """op::CvMatToOpInput for one scale: frames [n, h, w, 3] uint8 BGR (CUDA) ->
-        net_input [n, 3, net_h, net_w] float32 (CUDA)."""
-        n, h, w, c = frames.shape
-        assert c == 3 and frames.dtype == torch.uint8
+        net_input [n, 3, net_h, net_w] float32 (CUDA).  Frames with padded rows (a cv::Mat step)
+        come as [n, h, row bytes] with `width` pixels per row; the frames may be a view that
+        starts anywhere in a larger contiguous buffer (any base alignment)."""
+        n, h, w, step = _frame_rows(frames, width)
         assert net_input.shape[0] == n and net_input.shape[1] == 3
-        check(self.L.opk_cvmat_to_input(self.h, _ptr(net_input), _ptr(frames), n, w, h, w * 3,
+        check(self.L.opk_cvmat_to_input(self.h, _ptr(net_input), _ptr(frames), n, w, h, step,
                                         float(scale), net_input.shape[3], net_input.shape[2],
                                         normalize))
 
@@ -321,6 +353,29 @@ class Context:
         n, c, h, w = heat.shape
         check(self.L.opk_paf_scores(self.h, _ptr(scores), _ptr(heat), _ptr(peaks), n, pose_model, c,
                                     h, w, peaks.shape[2] - 1, inter_th, inter_min_above, nms_th))
+
+    def paf_scores_sources(self, out, sources, target_hw, peaks, pose_model=BODY_25,
+                           inter_th=CONNECT_INTER_THRESHOLD,
+                           inter_min_above=CONNECT_INTER_MIN_ABOVE_THRESHOLD, nms_th=NMS_THRESHOLD,
+                           semantics=MAPS_CPU, scale_ratios=None, rec_floats=0):
+        """The pipeline's PAF scorer on its lazy heat map (opk_paf_scores_sources): sources a list
+        of [N, C, h, w] net outputs resized to target_hw = (H, W) and averaged on the fly; peaks
+        [N, parts, maxPeaks+1, 3].  rec_floats 0: out is the dense [N, pairs, maxPeaks, maxPeaks]
+        array; else out is [N, rec_floats], one compact record per frame.  Returns the bytes of
+        the sources a workgroup stages on chip (0: read from memory)."""
+        n = len(sources)
+        ptrs = (ctypes.c_void_p * n)(*[_ptr(s).value for s in sources])
+        sizes = (ctypes.c_int * (4 * n))(*[int(v) for s in sources for v in s.shape])
+        ratios = None if scale_ratios is None else (ctypes.c_float * n)(*[float(r) for r in scale_ratios])
+        assert peaks.shape[0] == sources[0].shape[0] and peaks.dtype == torch.float32
+        assert out.dtype == torch.float32 and all(s.dtype == torch.float32 for s in sources)
+        assert rec_floats == 0 or out.numel() == peaks.shape[0] * rec_floats
+        staged = ctypes.c_size_t()
+        check(self.L.opk_paf_scores_sources(self.h, _ptr(out), rec_floats, ptrs, n, sizes,
+                                            target_hw[0], target_hw[1], semantics, ratios,
+                                            _ptr(peaks), pose_model, peaks.shape[2] - 1, inter_th,
+                                            inter_min_above, nms_th, ctypes.byref(staged)))
+        return staged.value
 
     def connect_body_parts(self, heat, peaks, pose_model=BODY_25, scale=1.0, max_people=512,
                            inter_min_above=CONNECT_INTER_MIN_ABOVE_THRESHOLD,

@@ -41,7 +41,8 @@ int dev_switch(const char* key, int dflt);
 // Launch log (tests and profiling: which kernel instantiation ran for which layer).  While a
 // log is attached to the calling thread, note_launch() appends "<layer>\t<kernel>" lines to it;
 // otherwise it returns at once.  NetHip attaches its log for the forwards run while the dev
-// switch LAUNCH_LOG is 1 (opk_net_launch_log).
+// switch LAUNCH_LOG is 1 (opk_net_launch_log) and puts the log attached before back afterwards;
+// opk_launch_log_begin / _end attach a log of the library's own (the launchers outside the net).
 struct LaunchLog {
     std::string layer;
     std::vector<std::string> lines;

@@ -271,6 +271,46 @@ int opk_paf_scores(opk_ctx* ctx, float* pair_scores, const float* heat, const fl
     });
 }
 
+int opk_paf_scores_sources(opk_ctx* ctx, float* out, int rec_floats, const float* const* sources,
+                           int nsrc, const int* ss, int target_h, int target_w, int semantics,
+                           const float* scale_ratios, const float* peaks, int pose_model,
+                           int max_peaks, float inter_th, float inter_min_above,
+                           float default_nms_th, size_t* staged_bytes)
+{
+    return guarded([&] {
+        OPK_CHECK_ARG(ctx && out && sources && ss && peaks, "NULL argument");
+        OPK_CHECK_ARG(semantics == OPK_MAPS_CPU || semantics == OPK_MAPS_CUDA,
+                      "unknown heat-map semantics");
+        OPK_CHECK_ARG(nsrc >= 1 && nsrc <= opk::kMaxResizeSources, "1..8 sources");
+        OPK_CHECK_ARG(rec_floats >= 0, "rec_floats: 0 (dense) or the record length");
+        const auto& m = opk::pose_model(pose_model);
+        int sh[opk::kMaxResizeSources], sw[opk::kMaxResizeSources];
+        for (int i = 0; i < nsrc; ++i) {
+            const int* s = ss + 4 * i;
+            OPK_CHECK_ARG(s[0] == ss[0] && s[1] == ss[1] && s[0] > 0,
+                          "source " + std::to_string(i) + " frames/channels differ from source 0");
+            OPK_CHECK_ARG(sources[i] != nullptr && s[2] > 0 && s[3] > 0, "empty source");
+            sh[i] = s[2];
+            sw[i] = s[3];
+        }
+        OPK_CHECK_ARG(ss[1] >= m.heat_channels(), "too few heat-map channels");
+        OPK_CHECK_ARG(target_h > 0 && target_w > 0, "empty target");
+        ctx->bind();
+        const opk::HeatMap heat = opk::lazy_heat_map(ctx, semantics, sources, sh, sw, nsrc, ss[1],
+                                                     target_h, target_w, scale_ratios);
+        const auto& t = ctx->pose_table(pose_model);
+        const double near = std::sqrt((double)(target_w * target_h)) / 150;
+        const float reject = float(default_nms_th + 1e-6);
+        if (staged_bytes) *staged_bytes = opk::paf_staged_bytes(heat);
+        if (rec_floats == 0)
+            opk::launch_paf_scores(out, heat, peaks, ss[0], max_peaks, t, inter_th, inter_min_above,
+                                   reject, near, ctx->stream);
+        else
+            opk::launch_paf_scores_compact(out, rec_floats, heat, peaks, ss[0], max_peaks, t,
+                                           inter_th, inter_min_above, reject, near, ctx->stream);
+    });
+}
+
 int opk_pose_model_info(int pose_model, int* parts, int* bkg, int* npairs, int* heat_channels,
                         int* pairs, int* map_idx)
 {

@@ -5,6 +5,7 @@
 #include <string>
 
 #include "../common.h"
+#include "context.h"
 
 namespace opk {
 
@@ -51,6 +52,26 @@ HeatMap cuda_heat_map(const float* const* src, const int* sh, const int* sw, int
         m.src[i].sy = main_h / s;
     }
     return m;
+}
+
+HeatMap lazy_heat_map(Context* ctx, int semantics, const float* const* src, const int* sh,
+                      const int* sw, int nsrc, int channels, int th, int tw,
+                      const float* scale_ratios)
+{
+    if (semantics == kMapsCuda)   // resizeAndMergeGpu's arithmetic
+        return cuda_heat_map(src, sh, sw, nsrc, channels, th, tw, scale_ratios);
+    OPK_CHECK_ARG(nsrc >= 1 && nsrc <= kMaxResizeSources, "1..8 sources");
+    HeatMap heat{};
+    heat.channels = channels;
+    heat.h = th;
+    heat.w = tw;
+    heat.nsrc = nsrc;
+    heat.inv_n = (float)(1. / (double)nsrc);
+    for (int i = 0; i < nsrc; ++i) {
+        const auto& t = ctx->tables(sh[i], sw[i], th, tw);
+        heat.src[i] = ResizeSource{src[i], sh[i], sw[i], t.yofs, t.ycoef, t.xofs, t.xcoef};
+    }
+    return heat;
 }
 
 }  // namespace opk

@@ -4,6 +4,8 @@
 
 namespace opk {
 
+struct Context;
+
 constexpr int kMapsCpu = 0;    // resizeAndMergeCpu + nmsCpu (OpenCV cubic A = -0.75, nmsCpu borders)
 constexpr int kMapsCuda = 1;   // resizeAndMergeGpu + nmsGpu (Catmull-Rom, strict interior)
 
@@ -16,5 +18,12 @@ constexpr int kMapsCuda = 1;   // resizeAndMergeGpu + nmsGpu (Catmull-Rom, stric
 //   (r = scaleInputToNetInputs), at most 8 sources.
 HeatMap cuda_heat_map(const float* const* src, const int* sh, const int* sw, int nsrc,
                       int channels, int th, int tw, const float* scale_ratios);
+
+// The lazy HeatMap the pipeline hands to NMS and the PAF scorer (PoseHip::submit_outputs, and
+// opk_paf_scores_sources): `semantics` kMapsCuda gives cuda_heat_map's, kMapsCpu the average of the
+// sources' cv::resize to th x tw through ctx's cubic tables (scale_ratios unused).
+HeatMap lazy_heat_map(Context* ctx, int semantics, const float* const* src, const int* sh,
+                      const int* sw, int nsrc, int channels, int th, int tw,
+                      const float* scale_ratios);
 
 }  // namespace opk

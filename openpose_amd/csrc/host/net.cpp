@@ -929,14 +929,17 @@ void NetHip::read_planes(const std::string& name, int f0, int nf, float* hi, flo
 void NetHip::forward_launches(ShapePlan& S, const float* input, int n, int h, int w, hipStream_t st)
 {
     const bool logging = dev_switch("LAUNCH_LOG", 0) != 0;
+    // the log attached before (opk_launch_log_begin) comes back after this forward
+    LaunchLog* const before = launch_log();
     if (logging) {
         log_.lines.clear();
         attach_launch_log(&log_);
     }
     struct Detach {
         bool on;
-        ~Detach() { if (on) attach_launch_log(nullptr); }
-    } detach{logging};
+        LaunchLog* before;
+        ~Detach() { if (on) attach_launch_log(before); }
+    } detach{logging, before};
     forward_steps(S, input, n, h, w, st);
 }
 

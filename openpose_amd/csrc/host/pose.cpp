@@ -574,30 +574,17 @@ void PoseHip::submit_outputs(const NetOutput* outs, int nscales, int n, int net_
     const int H = (int)std::round(((float)outs[0].h * nf - 1.f) * 1.f) + 1;
     const int W = (int)std::round(((float)outs[0].w * nf - 1.f) * 1.f) + 1;
     OPK_CHECK_ARG(H >= 1 && W >= 1, "upsampling ratio gives an empty heat map");
-    HeatMap heat{};
-    if (maps_ == kMapsCuda) {   // resizeAndMergeGpu's arithmetic (maps.h)
-        OPK_CHECK_ARG(nscales == 1 || have_ratios_,
-                      "multi-scale CUDA map semantics needs scaleInputToNetInputs (raw-frame path)");
-        const float* ptr[kMaxResizeSources];
-        int hs[kMaxResizeSources], ws[kMaxResizeSources];
-        for (int i = 0; i < nscales; ++i) {
-            ptr[i] = outs[i].ptr;
-            hs[i] = outs[i].h;
-            ws[i] = outs[i].w;
-        }
-        heat = cuda_heat_map(ptr, hs, ws, nscales, C, H, W, have_ratios_ ? map_ratios_ : nullptr);
-    } else {
-        heat.channels = C;
-        heat.h = H;
-        heat.w = W;
-        heat.nsrc = nscales;
-        heat.inv_n = (float)(1. / (double)nscales);
-        for (int i = 0; i < nscales; ++i) {
-            const auto& t = ctx_->tables(outs[i].h, outs[i].w, H, W);
-            heat.src[i] = ResizeSource{outs[i].ptr, outs[i].h, outs[i].w, t.yofs, t.ycoef, t.xofs,
-                                       t.xcoef};
-        }
+    OPK_CHECK_ARG(maps_ != kMapsCuda || nscales == 1 || have_ratios_,
+                  "multi-scale CUDA map semantics needs scaleInputToNetInputs (raw-frame path)");
+    const float* ptr[kMaxResizeSources];
+    int hs[kMaxResizeSources], ws[kMaxResizeSources];
+    for (int i = 0; i < nscales; ++i) {
+        ptr[i] = outs[i].ptr;
+        hs[i] = outs[i].h;
+        ws[i] = outs[i].w;
     }
+    const HeatMap heat = lazy_heat_map(ctx_, maps_, ptr, hs, ws, nscales, C, H, W,
+                                       have_ratios_ ? map_ratios_ : nullptr);
 
     // 2. scale net -> output (poseExtractorCaffe.cpp:281-310): mNetOutputSize = the net input
     //    size x (ratio / decrease factor), ratio 1 without --upsampling_ratio

@@ -140,22 +140,27 @@ void launch_cvmat_to_input(float* dst, const uint8_t* src, int n, int sh, int sw
                        src, sh, sw, src_step, frame, dh, dw, xt, yt, wtab, normalize, frame_of,  \
                        tab_stride, lds_row, (int)rows_at)
         if (ksize == 2) {
-            if (a16) OPK_WARP_LDS(2, true); else OPK_WARP_LDS(2, false);
+            if (a16) { note_launch("cvmat_to_input_lds<2,a16>"); OPK_WARP_LDS(2, true); }
+            else { note_launch("cvmat_to_input_lds<2>"); OPK_WARP_LDS(2, false); }
         } else {
-            if (a16) OPK_WARP_LDS(4, true); else OPK_WARP_LDS(4, false);
+            if (a16) { note_launch("cvmat_to_input_lds<4,a16>"); OPK_WARP_LDS(4, true); }
+            else { note_launch("cvmat_to_input_lds<4>"); OPK_WARP_LDS(4, false); }
         }
 #undef OPK_WARP_LDS
         OPK_LAUNCH_CHECK();
         return;
     }
-    if (ksize == 2)
+    if (ksize == 2) {
+        note_launch("cvmat_to_input<2>");
         hipLaunchKernelGGL(cvmat_to_input_kernel<2>, grid, dim3(threads), 0, stream, dst, src, sh,
                            sw, src_step, frame, dh, dw, xt, yt, wtab, normalize, frame_of,
                            tab_stride);
-    else
+    } else {
+        note_launch("cvmat_to_input<4>");
         hipLaunchKernelGGL(cvmat_to_input_kernel<4>, grid, dim3(threads), 0, stream, dst, src, sh,
                            sw, src_step, frame, dh, dw, xt, yt, wtab, normalize, frame_of,
                            tab_stride);
+    }
     OPK_LAUNCH_CHECK();
 }
 

@@ -79,6 +79,8 @@ void launch_paf_scores_compact(float* records, int rec_floats, const HeatMap& he
                                const float* peaks, int frames, int max_peaks,
                                const PafPairTable& t, float inter_th, float inter_min_above,
                                float reject_score, double near_dist, hipStream_t stream);
+// LDS bytes a workgroup of either launch stages for this map (0: the sources are read directly)
+size_t paf_staged_bytes(const HeatMap& heat);
 
 // ---- frame -> net input (input.hip) -------------------------------------------------------------
 // src: n BGR uint8 frames [sh][src_step bytes], frame stride src_step*sh; dst [n][3][dh][dw] fp32.

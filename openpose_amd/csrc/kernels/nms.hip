@@ -938,6 +938,7 @@ void launch_nms(float* peaks, int* scratch, const HeatMap& heat_in, int frames, 
     if (heat.heat) {
         const int quads = (w + 3) >> 2;
         dim3 g1((h * quads + DT - 1) / DT, parts, frames);
+        note_launch("nms_detect");
         hipLaunchKernelGGL(nms_detect_kernel, g1, dim3(DT), 0, stream, scratch, heat.heat,
                            heat.channels, parts, h, w, threshold, heat.cuda);
     } else if (!cuda && heat.nsrc <= 4 && dev_switch("NMS_STREAM", 1) != 0) {   // 0: dev A/B
@@ -966,11 +967,25 @@ void launch_nms(float* peaks, int* scratch, const HeatMap& heat_in, int frames, 
             hipLaunchKernelGGL((nms_detect_stream_kernel<lt, rc, NS_>), grid, dim3(lt), 0, stream, \
                                scratch, heat, parts, threshold);                               \
     } while (0)
+        // the route OPK_NMS_STREAM takes, by name (launch log)
         switch (heat.nsrc) {
-        case 1: OPK_NMS_STREAM(1); break;
-        case 2: OPK_NMS_STREAM(2); break;
-        case 3: OPK_NMS_STREAM(3); break;
-        default: OPK_NMS_STREAM(4); break;
+        case 1:
+            note_launch(!walk2 ? "nms_detect_stream<1>"
+                               : cold ? "nms_detect_walk2<1,cold>" : "nms_detect_walk2<1>");
+            OPK_NMS_STREAM(1);
+            break;
+        case 2:
+            note_launch(walk2 ? "nms_detect_walk2<2>" : "nms_detect_stream<2>");
+            OPK_NMS_STREAM(2);
+            break;
+        case 3:
+            note_launch(walk2 ? "nms_detect_walk2<3>" : "nms_detect_stream<3>");
+            OPK_NMS_STREAM(3);
+            break;
+        default:
+            note_launch(walk2 ? "nms_detect_walk2<4>" : "nms_detect_stream<4>");
+            OPK_NMS_STREAM(4);
+            break;
         }
 #undef OPK_NMS_STREAM
     } else {
@@ -978,6 +993,7 @@ void launch_nms(float* peaks, int* scratch, const HeatMap& heat_in, int frames, 
         // one-wave workgroups (64 columns, 62 tested): no workgroup barrier holds four waves on
         // each other and a CU keeps ~4x more windows' loads in flight (measured 752 -> 650-672 us
         // per 64-frame launch against 256-lane workgroups; 8 / 32-row windows 711 / 700 us)
+        note_launch("nms_detect_lazy");
         hipLaunchKernelGGL((nms_detect_lazy_kernel<loy, 64>),
                            dim3((w + 61) / 62, (h + loy - 1) / loy, frames * parts), dim3(64), 0,
                            stream, scratch, heat, parts, threshold);

@@ -354,6 +354,8 @@ size_t paf_lds_bytes(const HeatMap& M)
 
 }  // namespace
 
+size_t paf_staged_bytes(const HeatMap& heat) { return paf_lds_bytes(heat); }
+
 void launch_paf_scores(float* scores, const HeatMap& heat, const float* peaks, int frames,
                        int max_peaks, const PafPairTable& t, float inter_th,
                        float inter_min_above, float reject_score, double near_dist,
@@ -364,10 +366,20 @@ void launch_paf_scores(float* scores, const HeatMap& heat, const float* peaks, i
                           near_dist);
     const size_t lds = paf_lds_bytes(heat);
     const bool spl = dev_switch("PAF_SPL", 1) != 0;
-    if (lds && spl) hipLaunchKernelGGL((paf_dense_kernel<true, true>), dim3(t.npairs, frames), dim3(256), lds, stream, scores, a);
-    else if (lds) hipLaunchKernelGGL((paf_dense_kernel<true, false>), dim3(t.npairs, frames), dim3(256), lds, stream, scores, a);
-    else if (spl) hipLaunchKernelGGL((paf_dense_kernel<false, true>), dim3(t.npairs, frames), dim3(256), 0, stream, scores, a);
-    else hipLaunchKernelGGL((paf_dense_kernel<false, false>), dim3(t.npairs, frames), dim3(256), 0, stream, scores, a);
+    const dim3 grid(t.npairs, frames);
+    if (lds && spl) {
+        note_launch("paf_dense<lds,spl>");
+        hipLaunchKernelGGL((paf_dense_kernel<true, true>), grid, dim3(256), lds, stream, scores, a);
+    } else if (lds) {
+        note_launch("paf_dense<lds>");
+        hipLaunchKernelGGL((paf_dense_kernel<true, false>), grid, dim3(256), lds, stream, scores, a);
+    } else if (spl) {
+        note_launch("paf_dense<spl>");
+        hipLaunchKernelGGL((paf_dense_kernel<false, true>), grid, dim3(256), 0, stream, scores, a);
+    } else {
+        note_launch("paf_dense");
+        hipLaunchKernelGGL((paf_dense_kernel<false, false>), grid, dim3(256), 0, stream, scores, a);
+    }
     OPK_LAUNCH_CHECK();
 }
 
@@ -382,18 +394,23 @@ void launch_paf_scores_compact(float* records, int rec_floats, const HeatMap& he
     const size_t lds = paf_lds_bytes(heat);
     // PAF_SPL (dev A/B): 0 = one candidate line per lane
     const bool spl = dev_switch("PAF_SPL", 1) != 0;
-    if (lds && spl)
+    if (lds && spl) {
+        note_launch("paf_compact<lds,spl>");
         hipLaunchKernelGGL((paf_compact_kernel<true, true>), dim3(t.npairs, frames), dim3(256), lds, stream,
                            records, rec_floats, a);
-    else if (lds)
+    } else if (lds) {
+        note_launch("paf_compact<lds>");
         hipLaunchKernelGGL((paf_compact_kernel<true, false>), dim3(t.npairs, frames), dim3(256), lds, stream,
                            records, rec_floats, a);
-    else if (spl)
+    } else if (spl) {
+        note_launch("paf_compact<spl>");
         hipLaunchKernelGGL((paf_compact_kernel<false, true>), dim3(t.npairs, frames), dim3(256), 0, stream,
                            records, rec_floats, a);
-    else
+    } else {
+        note_launch("paf_compact");
         hipLaunchKernelGGL((paf_compact_kernel<false, false>), dim3(t.npairs, frames), dim3(256), 0, stream,
                            records, rec_floats, a);
+    }
     OPK_LAUNCH_CHECK();
 }
 

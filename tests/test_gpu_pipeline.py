@@ -17,9 +17,10 @@ import torch
 import oracle
 from oracle import body25
 from openpose_amd import synth
-from openpose_amd.api import Net, PoseExtractor, dev_switches
+from openpose_amd.api import Net, PoseExtractor, dev_switches, launch_log
 from openpose_amd.pose_tables import BODY_135, CONNECT_GPU
 from tests.golden.make_golden import connector_field
+from tests.kernel_routes import ran
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -405,7 +406,7 @@ def _multiscale_case(ctx, nscales, gap, seed, nms_stream=1, nms_walk=None, frame
     sw = dict(NMS_STREAM=nms_stream)
     if nms_walk is not None:
         sw["NMS_WALK"] = nms_walk
-    with dev_switches(**sw):
+    with dev_switches(**sw), launch_log() as log:
         pose.forward_multi([_dev(x) for x in xs], (1280, 720))
     s = pose.scale_net_to_output()
     assert abs(s - 1.959128) < 1e-5
@@ -422,6 +423,7 @@ def _multiscale_case(ctx, nscales, gap, seed, nms_stream=1, nms_walk=None, frame
         assert len(kp) >= 1
         np.testing.assert_array_equal(kp, rk)
         np.testing.assert_array_equal(ks, rs)
+    return log
 
 
 def test_multiscale_config4_bitexact(ctx):
@@ -438,7 +440,8 @@ def test_multiscale_config4_bitexact(ctx):
 def test_multiscale_other_scale_numbers_bitexact(ctx, nscales, gap, nms_stream):
     """--scale_number 2 / 3 (the 2- and 3-source streaming NMS walks) and 6 (more than 4 sources:
     the windowed lazy NMS), and the windowed kernel for 2-4 sources (NMS_STREAM=0)."""
-    _multiscale_case(ctx, nscales, gap, 40 + nscales, nms_stream)
+    log = _multiscale_case(ctx, nscales, gap, 40 + nscales, nms_stream)
+    ran(log, "nms_detect_walk2<%d>" % nscales if nms_stream and nscales <= 4 else "nms_detect_lazy")
 
 
 @pytest.mark.parametrize("walk", [0, 8])
@@ -447,7 +450,17 @@ def test_nms_walk_variants_bitexact(ctx, walk, nscales):
     """Both streaming NMS walks -- the two-columns-per-lane walk (nms_detect_walk2_kernel, the
     default) and the one-column ring walk (NMS_WALK=0) -- give the oracle's peaks and people, with
     1 and 4 sources (the other tests run the default)."""
-    _multiscale_case(ctx, nscales, 0.25, 90 + nscales, 1, walk)
+    log = _multiscale_case(ctx, nscales, 0.25, 90 + nscales, 1, walk)
+    ran(log, {(8, 1): "nms_detect_walk2<1,cold>", (8, 4): "nms_detect_walk2<4>",
+              (0, 1): "nms_detect_stream<1>", (0, 4): "nms_detect_stream<4>"}[(walk, nscales)])
+
+
+@pytest.mark.parametrize("nscales", [2, 3])
+def test_nms_ring_walk_two_three_sources(ctx, nscales):
+    """The one-column ring walk (NMS_WALK=0) with 2 and 3 sources: nms_detect_stream<2> and <3>,
+    which no other case reaches; the oracle's peaks and people."""
+    log = _multiscale_case(ctx, nscales, 0.25, 60 + nscales, 1, 0)
+    ran(log, "nms_detect_stream<%d>" % nscales)
 
 
 def test_collect_copy_sizes_adapt(ctx):
@@ -516,8 +529,9 @@ def test_nms_cold_windows_bitexact(ctx, kind):
     got = {}
     for cold in (1, 0):
         pose = PoseExtractor(ctx, None)
-        with dev_switches(NMS_COLD=cold):
+        with dev_switches(NMS_COLD=cold), launch_log() as log:
             pose.forward_net_output(_dev(f), (656, 368), (1280, 720))
+        ran(log, "nms_detect_walk2<1,cold>" if cold else "nms_detect_walk2<1>")
         got[cold] = pose.peaks_numpy()
         s = pose.scale_net_to_output()
         pose.close()

@@ -8,8 +8,9 @@ import torch
 
 import oracle
 from openpose_amd import pose_tables as pt
-from openpose_amd.api import dev_switches
+from openpose_amd.api import dev_switches, launch_log
 from tests.fields import noise_field, people_field, smooth_noise_field
+from tests.kernel_routes import ran
 
 pytestmark = pytest.mark.gpu
 
@@ -75,6 +76,18 @@ def test_nms_tiny_maps(ctx):
         peaks = torch.zeros((1, 25, 128, 3), device="cuda")
         ctx.nms(peaks, _dev(f[None]), 0.05)
         _peaks_equal(peaks.cpu().numpy()[0], oracle.nms(f, 0.05, 128))
+
+
+def test_nms_materialised_route(ctx):
+    """NMS of a materialised map (opk_nms) runs nms_detect, whatever the stream switches say; the
+    peaks are the oracle's."""
+    f = noise_field(78, 33, 47, seed=8)
+    peaks = torch.zeros((1, 25, 128, 3), device="cuda")
+    with launch_log() as log:
+        ctx.nms(peaks, _dev(f[None]), 0.05, (0.25, 0.5))
+    ran(log, "nms_detect")
+    assert [k for _, k in log] == ["nms_detect"]
+    _peaks_equal(peaks.cpu().numpy()[0], oracle.nms(f, 0.05, 128, (0.25, 0.5)))
 
 
 @pytest.mark.parametrize("spl", [1, 0])
