@@ -255,6 +255,49 @@ int opk_scale_and_size(int in_w, int in_h, int net_w, int net_h, float dynamic_b
 int opk_cvmat_to_input(opk_ctx* ctx, float* input_dev, const uint8_t* frames_dev, int n, int width,
                        int height, size_t step, double scale, int net_w, int net_h, int normalize);
 
+/* ---- Frames as the decoders leave them: packed BGR, or YUV 4:2:0 as NV12 (the hardware decode
+ * engines' surfaces) or I420 (software decoders).  Every function that takes `frames_dev, n, width,
+ * height, step` has a `_fmt` form taking this descriptor instead; the pointer-taking forms are the
+ * `_fmt` forms on a BGR descriptor {OPK_FRAMES_BGR, n, width, height, {frames_dev}, {step}, {0}}.
+ *
+ * ONE DEFINITION: with NV12 / I420 frames every `_fmt` function gives, bit for bit, what it gives
+ * on the BGR frames opk_frames_to_bgr makes of them -- the kernels convert what they read, no BGR
+ * copy is written.  In particular taps outside the image contribute BGR (0,0,0), not YUV (0,0,0).
+ *
+ * The conversion is the arithmetic of OpenCV's cvtColor(COLOR_YUV2BGR_NV12 / _I420): BT.601
+ * limited range in 20-bit fixed point; each 2x2 block of luma pixels shares one (U, V) pair
+ * (nearest chroma, no interpolation).  In int32, `>>` arithmetic:
+ *      y = max(0, Y - 16) * 1220542;   u = U - 128;   v = V - 128
+ *      B = clamp((y + (1 << 19) + 2116026 * u)               >> 20, 0, 255)
+ *      G = clamp((y + (1 << 19) -  852492 * v - 409993 * u)  >> 20, 0, 255)
+ *      R = clamp((y + (1 << 19) + 1673527 * v)               >> 20, 0, 255)
+ *
+ * plane / step / frame_bytes are per plane, so the decoder's surfaces (Y and UV of one frame
+ * adjacent, frames one surface apart) and plane-major batches are both described without a copy.
+ * The descriptor is read during the call only (a pipeline that needs the frames later keeps a
+ * copy of it); the planes follow the buffer rules of the pointer-taking form, the frame-lifetime
+ * rule of opk_pose_attach_extractor included: it holds for EVERY plane.
+ * OPK_ERR_ARG, before any device work: an unknown format; n < 0; a step shorter than its row; for
+ * NV12 / I420 an odd width or height, a NULL plane the format needs (n > 0), and I420 chroma
+ * planes with different steps.  n == 0 succeeds without device work where the pointer-taking form
+ * does. */
+#define OPK_FRAMES_BGR  0   /* plane[0]: [height][step[0]] packed BGR                      */
+#define OPK_FRAMES_NV12 1   /* plane[0]: Y [height][step[0]]; plane[1]: UV pairs, U first,  */
+                            /*           [height/2][step[1]]                                */
+#define OPK_FRAMES_I420 2   /* plane[0]: Y; plane[1]: U, plane[2]: V, [height/2][step[1|2]] */
+typedef struct opk_frames {
+    int format, n, width, height;
+    const uint8_t* plane[3];     /* device pointers of frame 0                              */
+    size_t step[3];              /* row bytes; 0 = tight (w*3 | w | w (NV12) | w/2 (I420))  */
+    size_t frame_bytes[3];       /* bytes from frame f to f+1 of that plane; 0 = step*rows  */
+} opk_frames;
+/* NV12 / I420 frames -> dst_dev BGR uint8 [n][height][dst_step] (dst_step 0 = width*3; only
+ * width*3 bytes of a row are written), enqueued on the context's stream.  BGR frames are
+ * OPK_ERR_ARG: there is nothing to convert. */
+int opk_frames_to_bgr(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, const opk_frames* frames);
+int opk_cvmat_to_input_fmt(opk_ctx* ctx, float* input_dev, const opk_frames* frames, double scale,
+                           int net_w, int net_h, int normalize);
+
 /* Kernel-variant switches (no reference counterpart; A/B tests and tuning only): key = one of
  * "CONV3_SMALL", "CONV3_W16", "CONV3_PERSIST", "CONV3_WIDE", "CONV3P_ASMR", "CONV3P_WIDE",
  * "CONV3P_PRIO", "CONV3W", "CONV1_TILE", "CONV1_N64W16", "CONV1_FUSED", "CONV3S_MAX" (read when a
@@ -474,6 +517,10 @@ int opk_pose_submit_frames(opk_pose* pose, const uint8_t* frames_dev, int n, int
                            int height, size_t step);
 int opk_pose_forward_frames(opk_pose* pose, const uint8_t* frames_dev, int n, int width,
                             int height, size_t step);
+/* The same on an opk_frames descriptor (BGR, NV12 or I420; see opk_frames).  The pipeline keeps a
+ * copy of the descriptor with the batch, not a pointer to it. */
+int opk_pose_submit_frames_fmt(opk_pose* pose, const opk_frames* frames);
+int opk_pose_forward_frames_fmt(opk_pose* pose, const opk_frames* frames);
 /* net input of scale i prepared by the last opk_pose_submit_frames ([n][3][net_h][net_w]) */
 int opk_pose_net_input(opk_pose* pose, int scale, const float** input_dev, int* net_w,
                        int* net_h);
@@ -601,6 +648,8 @@ int opk_extractor_heatmaps(opk_extractor* ex, const float** heatmaps_dev, int sh
 int opk_extractor_forward(opk_extractor* ex, const uint8_t* frames_dev, int nframes, int width,
                           int height, size_t step, const float* rects_host,
                           const int* frame_of_host, int people, float* keypoints_host);
+int opk_extractor_forward_fmt(opk_extractor* ex, const opk_frames* frames, const float* rects_host,
+                              const int* frame_of_host, int people, float* keypoints_host);
 /* crops of the last forward (order: hand, person, scale; skipped rectangles have none): the 2x3
  * inverse map (frame <- crop) and the crop's net input [3][net_h][net_w] on device */
 int opk_extractor_crop_count(opk_extractor* ex);
@@ -622,6 +671,8 @@ int opk_extractor_crop(opk_extractor* ex, int i, double* matrix_host, const floa
  * earlier submit queued, so the device stays busy during assembly and table building.
  * Frame lifetime (beside the stream contract of opk_pose_submit): THE FRAME BUFFER OF A SUBMITTED
  * BATCH MUST STAY UNCHANGED UNTIL THAT BATCH IS COLLECTED.
+ * (With an opk_frames descriptor that is every plane of it; the descriptor itself is copied at the
+ * submit and may go away.)
  * The stage warps each net batch's crops right before its forward, so it holds at most max_batch
  * crops of net input whatever the number of people and frames (same kernel, tables and stream
  * order as opk_extractor_forward: the same values); after a stage run opk_extractor_crop returns
@@ -727,6 +778,8 @@ int opk_render_pose_distance(opk_ctx* ctx, float* frame_dev, unsigned width, uns
                            255) -- clamp, then truncate toward zero                             */
 int opk_cvmat_to_output(opk_ctx* ctx, float* output_dev, const uint8_t* frames_dev, int n,
                         int width, int height, size_t step, double scale, int out_w, int out_h);
+int opk_cvmat_to_output_fmt(opk_ctx* ctx, float* output_dev, const opk_frames* frames, double scale,
+                            int out_w, int out_h);
 int opk_output_to_cvmat(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, const float* output_dev,
                         int n, int w, int h, int cast);
 
@@ -765,6 +818,15 @@ int opk_pose_render_frames(opk_pose* pose, uint8_t* dst_dev, size_t dst_step, in
                            const uint8_t* frames_dev, int n, int width, int height, size_t step,
                            double scale_input_to_output, float render_threshold, float alpha,
                            int googly_eyes, int blend_original, int cast);
+/* The same on opk_frames descriptors (see opk_frames); the drawn images stay BGR uint8. */
+int opk_render_frames_fmt(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, int out_w, int out_h,
+                          const opk_frames* frames, double scale_input_to_output,
+                          const opk_render_layer* layers, int n_layers, int blend_original,
+                          int cast);
+int opk_pose_render_frames_fmt(opk_pose* pose, uint8_t* dst_dev, size_t dst_step, int out_w,
+                               int out_h, const opk_frames* frames, double scale_input_to_output,
+                               float render_threshold, float alpha, int googly_eyes,
+                               int blend_original, int cast);
 /* opk_pose_render_frames with the face / hand stages' results (opk_pose_attach_extractor): the
  * collected batch as one POSE layer, then one FACE layer and one HAND layer, each only if its
  * extractor is attached, through opk_render_frames -- the bytes are opk_render_frames' for those
@@ -777,6 +839,12 @@ int opk_pose_render_frames_parts(opk_pose* pose, uint8_t* dst_dev, size_t dst_st
                                  float alpha, int googly_eyes, int blend_original, int cast,
                                  float face_threshold, float face_alpha, float hand_threshold,
                                  float hand_alpha);
+int opk_pose_render_frames_parts_fmt(opk_pose* pose, uint8_t* dst_dev, size_t dst_step, int out_w,
+                                     int out_h, const opk_frames* frames,
+                                     double scale_input_to_output, float render_threshold,
+                                     float alpha, int googly_eyes, int blend_original, int cast,
+                                     float face_threshold, float face_alpha, float hand_threshold,
+                                     float hand_alpha);
 
 /* The heat layer of opk_render_frames_heat: what one of opk_render_pose_heat_map / _heat_maps /
  * _paf / _pafs / _distance would draw on each frame, from frame f's own stack of heat_dev. */
@@ -832,6 +900,17 @@ int opk_pose_render_frames_element(opk_pose* pose, uint8_t* dst_dev, size_t dst_
                                    int element, float render_threshold, float alpha_keypoint,
                                    float alpha_heatmap, int googly_eyes, int blend_original,
                                    int cast);
+/* Both on opk_frames descriptors (see opk_frames). */
+int opk_render_frames_heat_fmt(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, int out_w,
+                               int out_h, const opk_frames* frames, double scale_input_to_output,
+                               const opk_render_layer* layers, int n_layers, int blend_original,
+                               int cast, const opk_render_heat* heat);
+int opk_pose_render_frames_element_fmt(opk_pose* pose, uint8_t* dst_dev, size_t dst_step, int out_w,
+                                       int out_h, const opk_frames* frames,
+                                       double scale_input_to_output, int element,
+                                       float render_threshold, float alpha_keypoint,
+                                       float alpha_heatmap, int googly_eyes, int blend_original,
+                                       int cast);
 
 #ifdef __cplusplus
 }

@@ -149,9 +149,29 @@ _SIGS = {
     "opk_render_frames_heat": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _i, _i, _i, _c.c_size_t, _d, _p,
                                     _i, _i, _i, _p]),
     "opk_render_element": (_i, [_i, _i, _ip, _ip]),
+    # the same on opk_frames descriptors (FramesStruct)
+    "opk_frames_to_bgr": (_i, [_p, _p, _c.c_size_t, _p]),
+    "opk_cvmat_to_input_fmt": (_i, [_p, _p, _p, _d, _i, _i, _i]),
+    "opk_pose_submit_frames_fmt": (_i, [_p, _p]),
+    "opk_pose_forward_frames_fmt": (_i, [_p, _p]),
+    "opk_extractor_forward_fmt": (_i, [_p, _p, _p, _p, _i, _p]),
+    "opk_cvmat_to_output_fmt": (_i, [_p, _p, _p, _d, _i, _i]),
+    "opk_render_frames_fmt": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _d, _p, _i, _i, _i]),
+    "opk_render_frames_heat_fmt": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _d, _p, _i, _i, _i, _p]),
+    "opk_pose_render_frames_fmt": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _d, _f, _f, _i, _i, _i]),
+    "opk_pose_render_frames_parts_fmt": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _d, _f, _f, _i, _i,
+                                              _i, _f, _f, _f, _f]),
+    "opk_pose_render_frames_element_fmt": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _d, _i, _f, _f,
+                                                _f, _i, _i, _i]),
     "opk_pose_render_frames_element": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _i, _i, _i,
                                             _c.c_size_t, _d, _i, _f, _f, _f, _i, _i, _i]),
 }
+
+
+class FramesStruct(ctypes.Structure):
+    """opk_frames (include/opk.h)."""
+    _fields_ = [("format", _i), ("n", _i), ("width", _i), ("height", _i), ("plane", _p * 3),
+                ("step", _c.c_size_t * 3), ("frame_bytes", _c.c_size_t * 3)]
 
 
 class RenderHeatStruct(ctypes.Structure):

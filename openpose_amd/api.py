@@ -87,6 +87,81 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+FRAMES_BGR, FRAMES_NV12, FRAMES_I420 = 0, 1, 2   # opk_frames.format (OPK_FRAMES_*)
+
+
+class Frames:
+    """A batch of frames as a decoder leaves it (opk_frames): packed BGR, NV12 (Y plane + interleaved
+    UV plane) or I420 (Y, U and V planes), as uint8 CUDA tensors [n, rows, row bytes] -- rows may be
+    padded (`width` pixels per row) and the frames any distance apart (tensor.stride(0)), so a
+    view into the decoder's surfaces works without a copy.  Every method that takes `frames`
+    accepts one; with NV12 / I420 it returns, bit for bit, what it returns on to_bgr()'s frames.
+    The planes must stay alive and unchanged as the tensor form's frames must."""
+
+    def __init__(self, fmt, planes, n, width, height):
+        self.format, self.planes, self.n, self.width, self.height = fmt, planes, n, width, height
+
+    @staticmethod
+    def _plane(t, n, rows, row_bytes, what):
+        assert t.dtype == torch.uint8 and t.is_cuda and t.dim() == 3, what + ": uint8 CUDA [n, rows, row bytes]"
+        assert t.shape[0] == n and t.shape[1] == rows and t.shape[2] >= row_bytes, what + ": shape"
+        assert t.stride(2) == 1 and (rows == 1 or t.stride(1) >= t.shape[2]), what + ": rows of bytes"
+        return t
+
+    @classmethod
+    def nv12(cls, y, uv, width=None):
+        """y [n, h, >= width], uv [n, h / 2, >= width] (U first); width default: y's row bytes."""
+        n, h = y.shape[0], y.shape[1]
+        w = y.shape[2] if width is None else width
+        assert w % 2 == 0 and h % 2 == 0, "YUV 4:2:0 frames need an even width and height"
+        return cls(FRAMES_NV12, [cls._plane(y, n, h, w, "y"), cls._plane(uv, n, h // 2, w, "uv")],
+                   n, w, h)
+
+    @classmethod
+    def i420(cls, y, u, v, width=None):
+        """y [n, h, >= width], u and v [n, h / 2, >= width / 2]; width default: y's row bytes."""
+        n, h = y.shape[0], y.shape[1]
+        w = y.shape[2] if width is None else width
+        assert w % 2 == 0 and h % 2 == 0, "YUV 4:2:0 frames need an even width and height"
+        return cls(FRAMES_I420, [cls._plane(y, n, h, w, "y"), cls._plane(u, n, h // 2, w // 2, "u"),
+                                 cls._plane(v, n, h // 2, w // 2, "v")], n, w, h)
+
+    @classmethod
+    def bgr(cls, t, width=None):
+        """t [n, h, w, 3], or [n, h, row bytes] with `width` pixels per row."""
+        n, h, w, _ = _frame_rows(t, width)
+        if t.dim() == 4:
+            assert t.stride(3) == 1 and t.stride(2) == 3, "packed BGR pixels"
+            t = t.as_strided((n, h, w * 3), (t.stride(0), t.stride(1), 1))
+        return cls(FRAMES_BGR, [cls._plane(t, n, h, w * 3, "bgr")], n, w, h)
+
+    @property
+    def device(self):
+        return self.planes[0].device
+
+    def struct(self):
+        """The opk_frames descriptor (a _lib.FramesStruct; the planes stay owned by self)."""
+        s = _lib.FramesStruct()
+        s.format, s.n, s.width, s.height = self.format, self.n, self.width, self.height
+        for i, t in enumerate(self.planes):
+            s.plane[i] = t.data_ptr()
+            # (a single row's stride says nothing; take it where it is a row step anyway)
+            s.step[i] = t.stride(1) if t.shape[1] > 1 or t.stride(1) >= t.shape[2] else t.shape[2]
+            s.frame_bytes[i] = t.stride(0) if self.n > 1 else 0
+        return s
+
+    def to_bgr(self, ctx, out=None):
+        """opk_frames_to_bgr: the BGR frames uint8 [n, h, w, 3] (or into the rows of `out`, uint8
+        [n, h, row bytes]) that every other method computes on."""
+        if out is None:
+            out = torch.empty((self.n, self.height, self.width, 3), dtype=torch.uint8,
+                              device=self.device)
+        s = self.struct()
+        check(ctx.L.opk_frames_to_bgr(ctx.h, _ptr(out), _row_bytes(out, self.n, self.height, self.width),
+                                      ctypes.byref(s)))
+        return out
+
+
 # Handles still open at interpreter exit (e.g. held by a test traceback) are closed before the HIP
 # runtime's own teardown: poses, then nets, then contexts.
 _LIVE = {"pose": weakref.WeakSet(), "extractor": weakref.WeakSet(), "net": weakref.WeakSet(),
@@ -208,7 +283,14 @@ class Context:
         """op::CvMatToOpInput for one scale: frames [n, h, w, 3] uint8 BGR (CUDA) ->
         net_input [n, 3, net_h, net_w] float32 (CUDA).  Frames with padded rows (a cv::Mat step)
         come as [n, h, row bytes] with `width` pixels per row; the frames may be a view that
-        starts anywhere in a larger contiguous buffer (any base alignment)."""
+        starts anywhere in a larger contiguous buffer (any base alignment).  Or a Frames."""
+        if isinstance(frames, Frames):
+            assert net_input.shape[0] == frames.n and net_input.shape[1] == 3
+            s = frames.struct()
+            check(self.L.opk_cvmat_to_input_fmt(self.h, _ptr(net_input), ctypes.byref(s),
+                                                float(scale), net_input.shape[3],
+                                                net_input.shape[2], normalize))
+            return
         n, h, w, step = _frame_rows(frames, width)
         assert net_input.shape[0] == n and net_input.shape[1] == 3
         check(self.L.opk_cvmat_to_input(self.h, _ptr(net_input), _ptr(frames), n, w, h, step,
@@ -279,7 +361,15 @@ class Context:
     # ---- the output image (CvMatToOpOutput / OpOutputToCvMat) and the fused batch render --------
     def cvmat_to_output(self, frames, scale=1.0, out_size=None):
         """op::CvMatToOpOutput for a batch: frames [n, h, w, 3] uint8 BGR (CUDA) -> float32
-        [n, out_h, out_w, 3]; out_size = (w, h), default the frames' own."""
+        [n, out_h, out_w, 3]; out_size = (w, h), default the frames' own.  Or a Frames."""
+        if isinstance(frames, Frames):
+            ow, oh = out_size if out_size is not None else (frames.width, frames.height)
+            out = torch.empty((frames.n, max(oh, 0), max(ow, 0), 3), dtype=torch.float32,
+                              device=frames.device)
+            s = frames.struct()
+            check(self.L.opk_cvmat_to_output_fmt(self.h, _ptr(out), ctypes.byref(s), float(scale),
+                                                 ow, oh))
+            return out
         n, h, w, c = frames.shape
         assert c == 3 and frames.dtype == torch.uint8
         ow, oh = out_size if out_size is not None else (w, h)
@@ -304,9 +394,13 @@ class Context:
         """CvMatToOpOutput -> the heat layer (a RenderHeat), if any -> the keypoint layers in
         order -> OpOutputToCvMat in one kernel: frames [n, h, w, 3] uint8 BGR (CUDA), layers a
         list of RenderLayer -> uint8 [n, out_h, out_w, 3] (or into the rows of `out`, uint8
-        [n, out_h, row bytes])."""
-        n, h, w, c = frames.shape
-        assert c == 3 and frames.dtype == torch.uint8
+        [n, out_h, row bytes]).  frames may be a Frames (BGR, NV12 or I420)."""
+        fs = frames.struct() if isinstance(frames, Frames) else None
+        if fs is not None:
+            n, h, w = frames.n, frames.height, frames.width
+        else:
+            n, h, w, c = frames.shape
+            assert c == 3 and frames.dtype == torch.uint8
         ow, oh = out_size if out_size is not None else (w, h)
         if out is None:
             out = torch.empty((n, max(oh, 0), max(ow, 0), 3), dtype=torch.uint8,
@@ -329,6 +423,11 @@ class Context:
             s.keypoints_dev = None if l.keypoints is None else _ptr(l.keypoints)
             s.counts_host = counts
             s.render_threshold, s.alpha, s.googly_eyes = l.threshold, l.alpha, int(l.googly_eyes)
+        if heat is None and fs is not None:
+            check(self.L.opk_render_frames_fmt(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow,
+                                               oh, ctypes.byref(fs), float(scale), arr,
+                                               len(layers), int(blend_original), cast))
+            return out
         if heat is None:
             check(self.L.opk_render_frames(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh,
                                            _ptr(frames), n, w, h, w * 3, float(scale), arr,
@@ -342,6 +441,12 @@ class Context:
             hs.heat_dev = _ptr(heat.heat)
             hs.channels, hs.heat_h, hs.heat_w = heat.heat.shape[1:]
         hs.scale_to_keep_ratio, hs.alpha = heat.scale, heat.alpha
+        if fs is not None:
+            check(self.L.opk_render_frames_heat_fmt(self.h, _ptr(out), _row_bytes(out, n, oh, ow),
+                                                    ow, oh, ctypes.byref(fs), float(scale), arr,
+                                                    len(layers), int(blend_original), cast,
+                                                    ctypes.byref(hs)))
+            return out
         check(self.L.opk_render_frames_heat(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh,
                                             _ptr(frames), n, w, h, w * 3, float(scale), arr,
                                             len(layers), int(blend_original), cast,
@@ -874,13 +979,19 @@ class PoseExtractor:
                                         float(dynamic_behavior), scale_number, float(scale_gap)))
 
     def _frames(self, fn, frames):
+        if isinstance(frames, Frames):
+            s = frames.struct()
+            check(getattr(self.L, fn.__name__ + "_fmt")(self.h, ctypes.byref(s)))
+            self._frames_n = frames.n
+            return
         n, h, w, c = frames.shape
         assert c == 3 and frames.dtype == torch.uint8
         check(fn(self.h, _ptr(frames), n, w, h, w * 3))
         self._frames_n = n
 
     def forward_frames(self, frames):
-        """Raw BGR uint8 frames [n, h, w, 3] (CUDA): GPU preprocessing + net + post-processing."""
+        """Raw BGR uint8 frames [n, h, w, 3] (CUDA), or a Frames (BGR, NV12, I420): GPU
+        preprocessing + net + post-processing."""
         self._frames(self.L.opk_pose_forward_frames, frames)
 
     def submit_frames(self, frames):
@@ -955,9 +1066,13 @@ class PoseExtractor:
         face / hands: also draw the attached extractors' results (attach) as a FACE and a HAND
         layer after the POSE layer (opk_pose_render_frames_parts when the flags name every attached
         extractor; a subset is put together from the accessors and drawn by Context.render_frames,
-        the same bytes)."""
-        n, h, w, c = frames.shape
-        assert c == 3 and frames.dtype == torch.uint8
+        the same bytes).  frames may be a Frames (BGR, NV12 or I420)."""
+        fs = frames.struct() if isinstance(frames, Frames) else None
+        if fs is not None:
+            n, h, w = frames.n, frames.height, frames.width
+        else:
+            n, h, w, c = frames.shape
+            assert c == 3 and frames.dtype == torch.uint8
         ow, oh = out_size if out_size is not None else (w, h)
         if out is None:
             out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
@@ -966,7 +1081,14 @@ class PoseExtractor:
                 raise ValueError("face / hand layers are drawn with the keypoints (element 0)")
             if (face and FACE not in self._attached) or (hands and HAND not in self._attached):
                 raise ValueError("no such extractor attached")
-            if bool(face) == (FACE in self._attached) and bool(hands) == (HAND in self._attached):
+            every = bool(face) == (FACE in self._attached) and bool(hands) == (HAND in self._attached)
+            if every and fs is not None:
+                check(self.L.opk_pose_render_frames_parts_fmt(
+                    self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh, ctypes.byref(fs),
+                    float(scale), threshold, alpha, int(googly_eyes), int(blend_original), cast,
+                    face_threshold, face_alpha, hand_threshold, hand_alpha))
+                return out
+            if every:
                 check(self.L.opk_pose_render_frames_parts(   # every attached extractor's layer
                     self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh, _ptr(frames), n, w, h,
                     w * 3, float(scale), threshold, alpha, int(googly_eyes), int(blend_original),
@@ -992,6 +1114,12 @@ class PoseExtractor:
                 layers.append(layer(LAYER_HAND, [self.hand_keypoints(f).reshape(-1, parts, 3)
                                                  for f in range(n)], 2, hand_threshold, hand_alpha))
             return self.ctx.render_frames(frames, layers, scale, out_size, blend_original, cast, out)
+        if fs is not None:
+            check(self.L.opk_pose_render_frames_element_fmt(
+                self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh, ctypes.byref(fs),
+                float(scale), int(element), threshold, alpha, alpha_heatmap, int(googly_eyes),
+                int(blend_original), cast))
+            return out
         check(self.L.opk_pose_render_frames_element(
             self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh, _ptr(frames), n, w, h, w * 3,
             float(scale), int(element), threshold, alpha, alpha_heatmap, int(googly_eyes),
@@ -1163,9 +1291,11 @@ class KeypointExtractor:
     def forward(self, frames, rectangles, frame_of=None):
         """frames: BGR uint8 [n, h, w, 3] CUDA tensor; rectangles [people, 4] (face) or
         [people, 2, 4] (hand); frame_of [people] or None.  Returns face [people, parts, 3] or
-        hand [2, people, parts, 3] keypoints (numpy)."""
-        n, h, w, c = frames.shape
-        assert c == 3 and frames.dtype == torch.uint8
+        hand [2, people, parts, 3] keypoints (numpy).  frames may be a Frames."""
+        fs = frames.struct() if isinstance(frames, Frames) else None
+        if fs is None:
+            n, h, w, c = frames.shape
+            assert c == 3 and frames.dtype == torch.uint8
         r = np.ascontiguousarray(rectangles, np.float32)
         people = r.shape[0]
         hands = 2 if self.kind == HAND else 1
@@ -1174,6 +1304,12 @@ class KeypointExtractor:
         if frame_of is not None:
             fo = np.ascontiguousarray(frame_of, np.int32)
             assert fo.shape == (people,)
+        if fs is not None:
+            check(self.L.opk_extractor_forward_fmt(
+                self.h, ctypes.byref(fs), r.ctypes.data_as(ctypes.c_void_p),
+                fo.ctypes.data_as(ctypes.c_void_p) if fo is not None else None, people,
+                out.ctypes.data_as(ctypes.c_void_p)))
+            return out[0] if self.kind == FACE else out
         check(self.L.opk_extractor_forward(
             self.h, _ptr(frames), n, w, h, w * 3, r.ctypes.data_as(ctypes.c_void_p),
             fo.ctypes.data_as(ctypes.c_void_p) if fo is not None else None, people,

@@ -490,16 +490,24 @@ int opk_scale_and_size(int in_w, int in_h, int net_w, int net_h, float dynamic_b
     });
 }
 
-int opk_cvmat_to_input(opk_ctx* ctx, float* input_dev, const uint8_t* frames_dev, int n, int width,
-                       int height, size_t step, double scale, int net_w, int net_h, int normalize)
+int opk_cvmat_to_input_fmt(opk_ctx* ctx, float* input_dev, const opk_frames* frames, double scale,
+                           int net_w, int net_h, int normalize)
 {
     return guarded_net([&] {
         OPK_CHECK_ARG(ctx, "NULL context");
+        OPK_CHECK_ARG(frames, "NULL frames");
         OPK_CHECK_ARG(normalize == 0 || normalize == 1,
                       "normalize: 0 (none) or 1 (VGG); DenseNet (2) is not supported");
-        opk::cvmat_to_input(ctx, input_dev, frames_dev, n, width, height, step, scale, net_w, net_h,
+        opk::cvmat_to_input(ctx, input_dev, opk::frame_source(*frames), scale, net_w, net_h,
                             normalize);
     });
+}
+
+int opk_cvmat_to_input(opk_ctx* ctx, float* input_dev, const uint8_t* frames_dev, int n, int width,
+                       int height, size_t step, double scale, int net_w, int net_h, int normalize)
+{
+    const opk_frames f = opk::bgr_descriptor(frames_dev, n, width, height, step);
+    return opk_cvmat_to_input_fmt(ctx, input_dev, &f, scale, net_w, net_h, normalize);
 }
 
 int opk_pose_set_input(opk_pose* p, int net_w, int net_h, float dynamic_behavior, int scale_number,
@@ -511,31 +519,47 @@ int opk_pose_set_input(opk_pose* p, int net_w, int net_h, float dynamic_behavior
     });
 }
 
-int opk_pose_submit_frames(opk_pose* p, const uint8_t* frames, int n, int width, int height,
-                           size_t step)
+int opk_pose_submit_frames_fmt(opk_pose* p, const opk_frames* frames)
 {
     return guarded_net([&] {
         OPK_CHECK_ARG(p, "NULL pose");
-        p->pose->submit_frames(frames, n, width, height, step);
+        OPK_CHECK_ARG(frames, "NULL frames");
+        p->pose->submit_frames(opk::frame_source(*frames));
     });
+}
+
+int opk_pose_forward_frames_fmt(opk_pose* p, const opk_frames* frames)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        OPK_CHECK_ARG(frames, "NULL frames");
+        p->pose->forward_frames(opk::frame_source(*frames));
+    });
+}
+
+int opk_pose_submit_frames(opk_pose* p, const uint8_t* frames, int n, int width, int height,
+                           size_t step)
+{
+    const opk_frames f = opk::bgr_descriptor(frames, n, width, height, step);
+    return opk_pose_submit_frames_fmt(p, &f);
 }
 
 int opk_pose_forward_frames(opk_pose* p, const uint8_t* frames, int n, int width, int height,
                             size_t step)
 {
-    return guarded_net([&] {
-        OPK_CHECK_ARG(p, "NULL pose");
-        p->pose->forward_frames(frames, n, width, height, step);
-    });
+    const opk_frames f = opk::bgr_descriptor(frames, n, width, height, step);
+    return opk_pose_forward_frames_fmt(p, &f);
 }
 
-int opk_pose_render_frames(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w, int out_h,
-                           const uint8_t* frames, int n, int width, int height, size_t step,
-                           double scale, float threshold, float alpha, int googly_eyes,
-                           int blend_original, int cast)
+int opk_pose_render_frames_fmt(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w, int out_h,
+                               const opk_frames* frames, double scale, float threshold, float alpha,
+                               int googly_eyes, int blend_original, int cast)
 {
     return guarded_net([&] {
         OPK_CHECK_ARG(p, "NULL pose");
+        OPK_CHECK_ARG(frames, "NULL frames");
+        const opk::FrameSource src = opk::frame_source(*frames);
+        const int n = src.n;
         std::vector<int> counts;
         opk_render_layer layer{};
         const opk::PoseHip& pose = *p->pose;
@@ -565,23 +589,35 @@ int opk_pose_render_frames(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w
         layer.render_threshold = threshold;
         layer.alpha = alpha;
         layer.googly_eyes = googly_eyes;
-        opk::render_frames(p->ctx, dst, dst_step, out_w, out_h, frames, n, width, height, step,
-                           scale, &layer, 1, blend_original, cast, kp.data(), kp.size());
+        opk::render_frames(p->ctx, dst, dst_step, out_w, out_h, src, scale, &layer, 1,
+                           blend_original, cast, kp.data(), kp.size());
     });
 }
 
-int opk_pose_render_frames_element(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w,
-                                   int out_h, const uint8_t* frames, int n, int width, int height,
-                                   size_t step, double scale, int element, float threshold,
-                                   float alpha_keypoint, float alpha_heatmap, int googly_eyes,
-                                   int blend_original, int cast)
+int opk_pose_render_frames(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w, int out_h,
+                           const uint8_t* frames, int n, int width, int height, size_t step,
+                           double scale, float threshold, float alpha, int googly_eyes,
+                           int blend_original, int cast)
+{
+    const opk_frames f = opk::bgr_descriptor(frames, n, width, height, step);
+    return opk_pose_render_frames_fmt(p, dst, dst_step, out_w, out_h, &f, scale, threshold, alpha,
+                                      googly_eyes, blend_original, cast);
+}
+
+int opk_pose_render_frames_element_fmt(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w,
+                                       int out_h, const opk_frames* frames, double scale,
+                                       int element, float threshold, float alpha_keypoint,
+                                       float alpha_heatmap, int googly_eyes, int blend_original,
+                                       int cast)
 {
     if (element == 0)
-        return opk_pose_render_frames(p, dst, dst_step, out_w, out_h, frames, n, width, height,
-                                      step, scale, threshold, alpha_keypoint, googly_eyes,
-                                      blend_original, cast);
+        return opk_pose_render_frames_fmt(p, dst, dst_step, out_w, out_h, frames, scale, threshold,
+                                          alpha_keypoint, googly_eyes, blend_original, cast);
     return guarded_net([&] {
         OPK_CHECK_ARG(p, "NULL pose");
+        OPK_CHECK_ARG(frames, "NULL frames");
+        const opk::FrameSource src = opk::frame_source(*frames);
+        const int n = src.n;
         const opk::PoseHip& pose = *p->pose;
         opk_render_heat heat{};
         heat.pose_model = pose.model();
@@ -596,9 +632,21 @@ int opk_pose_render_frames_element(opk_pose* p, uint8_t* dst, size_t dst_step, i
         // so the frame is never cleared
         heat.scale_to_keep_ratio = pose.scale_net_to_output() * (float)scale;
         heat.alpha = blend_original ? alpha_heatmap : 1.f;
-        opk::render_frames(p->ctx, dst, dst_step, out_w, out_h, frames, n, width, height, step,
-                           scale, nullptr, 0, 1, cast, nullptr, 0, &heat, &lazy);
+        opk::render_frames(p->ctx, dst, dst_step, out_w, out_h, src, scale, nullptr, 0, 1, cast,
+                           nullptr, 0, &heat, &lazy);
     });
+}
+
+int opk_pose_render_frames_element(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w,
+                                   int out_h, const uint8_t* frames, int n, int width, int height,
+                                   size_t step, double scale, int element, float threshold,
+                                   float alpha_keypoint, float alpha_heatmap, int googly_eyes,
+                                   int blend_original, int cast)
+{
+    const opk_frames f = opk::bgr_descriptor(frames, n, width, height, step);
+    return opk_pose_render_frames_element_fmt(p, dst, dst_step, out_w, out_h, &f, scale, element,
+                                              threshold, alpha_keypoint, alpha_heatmap, googly_eyes,
+                                              blend_original, cast);
 }
 
 int opk_pose_net_input(opk_pose* p, int scale, const float** input_dev, int* net_w, int* net_h)
@@ -713,15 +761,22 @@ int opk_extractor_heatmaps(opk_extractor* ex, const float** heatmaps_dev, int sh
     });
 }
 
+int opk_extractor_forward_fmt(opk_extractor* ex, const opk_frames* frames, const float* rects,
+                              const int* frame_of, int people, float* keypoints)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(ex && frames && (people == 0 || keypoints), "NULL argument");
+        ex->ex->extract(opk::frame_source(*frames), reinterpret_cast<const opk::Rect*>(rects),
+                        frame_of, people, keypoints);
+    });
+}
+
 int opk_extractor_forward(opk_extractor* ex, const uint8_t* frames, int nframes, int width,
                           int height, size_t step, const float* rects, const int* frame_of,
                           int people, float* keypoints)
 {
-    return guarded_net([&] {
-        OPK_CHECK_ARG(ex && (people == 0 || keypoints), "NULL argument");
-        ex->ex->extract(frames, nframes, width, height, step,
-                        reinterpret_cast<const opk::Rect*>(rects), frame_of, people, keypoints);
-    });
+    const opk_frames f = opk::bgr_descriptor(frames, nframes, width, height, step);
+    return opk_extractor_forward_fmt(ex, &f, rects, frame_of, people, keypoints);
 }
 
 int opk_extractor_crop_count(opk_extractor* ex) { return ex ? ex->ex->crops() : -1; }
@@ -795,14 +850,17 @@ int opk_pose_read_part_times(opk_pose* p, int kind, int* batches, int* crops, do
     });
 }
 
-int opk_pose_render_frames_parts(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w, int out_h,
-                                 const uint8_t* frames, int n, int width, int height, size_t step,
-                                 double scale, float threshold, float alpha, int googly_eyes,
-                                 int blend_original, int cast, float face_threshold,
-                                 float face_alpha, float hand_threshold, float hand_alpha)
+int opk_pose_render_frames_parts_fmt(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w,
+                                     int out_h, const opk_frames* frames, double scale,
+                                     float threshold, float alpha, int googly_eyes,
+                                     int blend_original, int cast, float face_threshold,
+                                     float face_alpha, float hand_threshold, float hand_alpha)
 {
     return guarded_net([&] {
         OPK_CHECK_ARG(p, "NULL pose");
+        OPK_CHECK_ARG(frames, "NULL frames");
+        const opk::FrameSource src = opk::frame_source(*frames);
+        const int n = src.n;
         opk::PoseHip& pose = *p->pose;
         if (pose.frames() == 0) throw opk::Error(OPK_ERR_STATE, "no collected batch to render");
         if (n != pose.frames())
@@ -866,9 +924,21 @@ int opk_pose_render_frames_parts(opk_pose* p, uint8_t* dst, size_t dst_step, int
             layers[nl].alpha = kind == OPK_EXTRACT_HAND ? hand_alpha : face_alpha;
             ++nl;
         }
-        opk::render_frames(p->ctx, dst, dst_step, out_w, out_h, frames, n, width, height, step,
-                           scale, layers, nl, blend_original, cast, kp[0].data(), kp[0].size());
+        opk::render_frames(p->ctx, dst, dst_step, out_w, out_h, src, scale, layers, nl,
+                           blend_original, cast, kp[0].data(), kp[0].size());
     });
+}
+
+int opk_pose_render_frames_parts(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w, int out_h,
+                                 const uint8_t* frames, int n, int width, int height, size_t step,
+                                 double scale, float threshold, float alpha, int googly_eyes,
+                                 int blend_original, int cast, float face_threshold,
+                                 float face_alpha, float hand_threshold, float hand_alpha)
+{
+    const opk_frames f = opk::bgr_descriptor(frames, n, width, height, step);
+    return opk_pose_render_frames_parts_fmt(p, dst, dst_step, out_w, out_h, &f, scale, threshold,
+                                            alpha, googly_eyes, blend_original, cast,
+                                            face_threshold, face_alpha, hand_threshold, hand_alpha);
 }
 
 }  // extern "C"

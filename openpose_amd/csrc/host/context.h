@@ -87,8 +87,8 @@ struct Context {
 // heat (may be NULL): the heat layer of opk_render_frames_heat; with `lazy` its values come from
 // that map instead of heat->heat_dev (opk_pose_render_frames_element), whose size fields it sets.
 void render_frames(Context* ctx, uint8_t* dst, size_t dst_step, int out_w, int out_h,
-                   const uint8_t* frames, int n, int width, int height, size_t step, double scale,
-                   const ::opk_render_layer* layers, int n_layers, int blend_original, int cast,
+                   const FrameSource& frames, double scale, const ::opk_render_layer* layers,
+                   int n_layers, int blend_original, int cast,
                    const float* kp_host = nullptr, size_t kp_floats = 0,
                    const ::opk_render_heat* heat = nullptr, const HeatMap* lazy = nullptr);
 // opk_render_element (host/render.cpp): OPK_HEAT_* kind and channel of a renderPose element

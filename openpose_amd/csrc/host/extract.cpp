@@ -199,18 +199,16 @@ const float* KeypointExtractor::heatmaps(int shape[5]) const
     return static_cast<const float*>(heat_out_.ptr);
 }
 
-void KeypointExtractor::extract(const uint8_t* frames, int nframes, int w, int h, size_t step,
-                                const Rect* rects, const int* frame_of, int people,
-                                float* keypoints, bool chunked)
+void KeypointExtractor::extract(const FrameSource& frames, const Rect* rects, const int* frame_of,
+                                int people, float* keypoints, bool chunked)
 {
+    const int nframes = frames.n, w = frames.w, h = frames.h;
     const auto t_start = std::chrono::steady_clock::now();
     host_ms_ = wait_ms_ = 0.;
     OPK_CHECK_ARG(ctx_->device >= 0, "extraction needs a device context");
     OPK_CHECK_ARG(people >= 0, "negative people");
     OPK_CHECK_ARG(nframes > 0 && w > 0 && h > 0, "Empty cvInputData.");
-    OPK_CHECK_ARG(frames, "NULL frames");
-    if (!step) step = (size_t)w * 3;
-    OPK_CHECK_ARG(step >= (size_t)w * 3, "row step shorter than the row");
+    OPK_CHECK_ARG(frames.plane[0], "NULL frames");
     const int hands = kind_ == kHand ? 2 : 1;
     const int P = parts();
     OPK_CHECK_ARG(P > 0, "net has no part channels");
@@ -290,7 +288,7 @@ void KeypointExtractor::extract(const uint8_t* frames, int nframes, int w, int h
     const int* frame_tab = tabs + (size_t)n * tw * 2;
     auto warp = [&](float* dst, int first, int count) {
         const int* t = tabs + (size_t)first * tw * 2;
-        launch_cvmat_to_input(dst, frames, count, h, w, step, net_h_, net_w_, t, t + 2 * net_w_,
+        launch_cvmat_to_input(dst, frames, count, net_h_, net_w_, t, t + 2 * net_w_,
                               ctx_->warp_weight_table(false), 2, 1, s, frame_tab + first, tw);
     };
     if (!chunked) warp(in, 0, n);

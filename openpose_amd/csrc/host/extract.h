@@ -43,7 +43,8 @@ public:
     void set_heatmaps(int scale_mode);
     const float* heatmaps(int shape[5]) const;
 
-    // frames: BGR uint8 [nframes][h][step] on device; rects on the host: face [people],
+    // frames: BGR uint8 [nframes][h][step] on device, or NV12 / I420 (converted inside the crop
+    // warp: the values of the BGR frames they convert to); rects on the host: face [people],
     // hand [people][2]; frame_of[people] (NULL: all frame 0).  keypoints (host): face
     // [people][parts][3], hand [2][people][parts][3] (left hands first); zeros for the rectangles
     // the reference skips.
@@ -51,8 +52,8 @@ public:
     // forward into a buffer of max_batch crops -- same kernel, tables and stream order, so the
     // same values -- instead of every crop of the call before the first batch; crop_inputs() is
     // then NULL.
-    void extract(const uint8_t* frames, int nframes, int w, int h, size_t step, const Rect* rects,
-                 const int* frame_of, int people, float* keypoints, bool chunked = false);
+    void extract(const FrameSource& frames, const Rect* rects, const int* frame_of, int people,
+                 float* keypoints, bool chunked = false);
     // wall milliseconds of the last extract(): host work (crop validity, inverse maps, tables),
     // then everything that can block on the device -- the table upload, the enqueue of every net
     // batch (launches wait for room in the queue) and the final synchronisation

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../../include/opk.h"
 #include "../common.h"
 #include "../kernels/kernels.h"
 #include "context.h"
@@ -174,10 +175,58 @@ const Context::WarpAxes& Context::warp_axis_tables(double scale, int dw, int dh)
     return ref;
 }
 
-void cvmat_to_input(Context* ctx, float* dst, const uint8_t* src, int n, int sw, int sh,
-                    size_t step, double scale, int dw, int dh, int normalize, hipStream_t stream)
+FrameSource frame_source(const ::opk_frames& d)
 {
-    OPK_CHECK_ARG(dst && src, "NULL buffer");
+    static_assert(OPK_FRAMES_BGR == kFramesBgr && OPK_FRAMES_NV12 == kFramesNv12 &&
+                      OPK_FRAMES_I420 == kFramesI420,
+                  "OPK_FRAMES_* are FrameFormat's values");
+    OPK_CHECK_ARG(d.format == OPK_FRAMES_BGR || d.format == OPK_FRAMES_NV12 ||
+                      d.format == OPK_FRAMES_I420,
+                  "unknown frame format: OPK_FRAMES_BGR (0), OPK_FRAMES_NV12 (1) or OPK_FRAMES_I420 (2)");
+    OPK_CHECK_ARG(d.n >= 0, "negative frame count");
+    FrameSource s{};
+    s.format = d.format;
+    s.n = d.n;
+    s.w = d.width;
+    s.h = d.height;
+    const size_t w = d.width > 0 ? (size_t)d.width : 0, h = d.height > 0 ? (size_t)d.height : 0;
+    if (d.format == OPK_FRAMES_BGR) {
+        OPK_CHECK_ARG(d.step[0] == 0 || d.step[0] >= w * 3, "row step shorter than the row");
+        s.plane[0] = d.plane[0];
+        s.step = d.step[0] ? d.step[0] : w * 3;
+        s.frame[0] = d.frame_bytes[0] ? d.frame_bytes[0] : s.step * h;
+        return s;
+    }
+    OPK_CHECK_ARG(d.width % 2 == 0 && d.height % 2 == 0,
+                  "YUV 4:2:0 frames need an even width and height");
+    const bool nv12 = d.format == OPK_FRAMES_NV12;
+    const size_t crow = nv12 ? w : w / 2;   // bytes of a chroma row
+    OPK_CHECK_ARG(d.step[0] == 0 || d.step[0] >= w, "row step shorter than the row");
+    OPK_CHECK_ARG(d.step[1] == 0 || d.step[1] >= crow, "row step shorter than the row");
+    OPK_CHECK_ARG(nv12 || d.step[2] == 0 || d.step[2] >= crow, "row step shorter than the row");
+    if (d.n > 0)
+        OPK_CHECK_ARG(d.plane[0] && d.plane[1] && (nv12 || d.plane[2]),
+                      nv12 ? "NULL plane: NV12 frames need plane[0] (Y) and plane[1] (UV)"
+                           : "NULL plane: I420 frames need plane[0] (Y), plane[1] (U) and plane[2] (V)");
+    s.step = d.step[0] ? d.step[0] : w;
+    s.cstep = d.step[1] ? d.step[1] : crow;
+    OPK_CHECK_ARG(nv12 || (d.step[2] ? d.step[2] : crow) == s.cstep,
+                  "the U and V planes of I420 frames share one row step");
+    s.cpix = nv12 ? 2 : 1;
+    s.plane[0] = d.plane[0];
+    s.plane[1] = d.plane[1];
+    s.plane[2] = nv12 ? (d.plane[1] ? d.plane[1] + 1 : nullptr) : d.plane[2];
+    s.frame[0] = d.frame_bytes[0] ? d.frame_bytes[0] : s.step * h;
+    s.frame[1] = d.frame_bytes[1] ? d.frame_bytes[1] : s.cstep * (h / 2);
+    s.frame[2] = nv12 ? s.frame[1] : (d.frame_bytes[2] ? d.frame_bytes[2] : s.cstep * (h / 2));
+    return s;
+}
+
+void cvmat_to_input(Context* ctx, float* dst, const FrameSource& src, double scale, int dw, int dh,
+                    int normalize, hipStream_t stream)
+{
+    const int n = src.n, sw = src.w, sh = src.h;
+    OPK_CHECK_ARG(dst && src.plane[0], "NULL buffer");
     OPK_CHECK_ARG(n > 0 && sw > 0 && sh > 0 && dw > 0 && dh > 0, "empty frame or net input");
     OPK_CHECK_ARG(scale > 0 && std::isfinite(scale), "scale must be positive");
     ctx->bind();
@@ -187,8 +236,8 @@ void cvmat_to_input(Context* ctx, float* dst, const uint8_t* src, int n, int sw,
     const bool cubic = scale > 1.;
     const short* w = ctx->warp_weight_table(cubic);
     const auto& ax = ctx->warp_axis_tables(scale, dw, dh);
-    launch_cvmat_to_input(dst, src, n, sh, sw, step ? step : (size_t)sw * 3, dh, dw, ax.x, ax.y, w,
-                          cubic ? 4 : 2, normalize, stream ? stream : ctx->stream);
+    launch_cvmat_to_input(dst, src, n, dh, dw, ax.x, ax.y, w, cubic ? 4 : 2, normalize,
+                          stream ? stream : ctx->stream);
 }
 
 }  // namespace opk

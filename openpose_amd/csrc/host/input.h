@@ -4,6 +4,9 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "../../../include/opk.h"
+#include "../kernels/kernels.h"
+
 namespace opk {
 
 struct Context;
@@ -22,11 +25,31 @@ void scale_and_size(int in_w, int in_h, int net_w, int net_h, float dyn, int sca
 void warp_weight_table(bool cubic, short* itab);
 void warp_axis_table(double scale, int d, bool cubic, int* tab /* 2*d */);
 
-// op::CvMatToOpInput::createArray for one scale (cvMatToOpInput.cpp:63-98), a batch of n frames:
-// src BGR uint8 [n][sh][step bytes] on device -> dst [n][3][dh][dw] fp32 on device
+// An opk_frames descriptor (include/opk.h) checked and resolved, before any device work: unknown
+// format, n < 0, a step shorter than its row, and for NV12 / I420 an odd width or height and (n > 0)
+// a NULL plane are OPK_ERR_ARG; steps and frame strides of 0 get their tight values, NV12's V plane
+// is U + 1.  Sizes <= 0 and a NULL BGR buffer are left to the callers' own checks, which the
+// pointer-taking entry points share.  The result holds no pointer into the descriptor.
+FrameSource frame_source(const ::opk_frames& frames);
+// the descriptor the pointer-taking entry points fill: n BGR frames [height][step bytes]
+inline ::opk_frames bgr_descriptor(const uint8_t* frames, int n, int width, int height, size_t step)
+{
+    ::opk_frames d{};
+    d.format = OPK_FRAMES_BGR;
+    d.n = n;
+    d.width = width;
+    d.height = height;
+    d.plane[0] = frames;
+    d.step[0] = step;
+    return d;
+}
+
+// op::CvMatToOpInput::createArray for one scale (cvMatToOpInput.cpp:63-98), a batch of src.n
+// frames on device (BGR, or NV12 / I420 converted inside the warp: the values of the BGR path on
+// opk_frames_to_bgr's output) -> dst [n][3][dh][dw] fp32 on device
 // (resizeFixedAspectRatio + uCharCvMatToFloatPtr with the VGG normalisation when normalize != 0).
 // (stream: where the warp runs; nullptr = the context's stream)
-void cvmat_to_input(Context* ctx, float* dst, const uint8_t* src, int n, int sw, int sh,
-                    size_t step, double scale, int dw, int dh, int normalize, hipStream_t stream = nullptr);
+void cvmat_to_input(Context* ctx, float* dst, const FrameSource& src, double scale, int dw, int dh,
+                    int normalize, hipStream_t stream = nullptr);
 
 }  // namespace opk

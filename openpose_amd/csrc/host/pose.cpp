@@ -264,7 +264,7 @@ void PoseHip::forward_net_output(const float* net_out, int n, int oh, int ow, in
 
 void PoseHip::need_frames() const
 {
-    if (any_attached() && !cur_raw_.ptr)
+    if (any_attached() && !cur_raw_.plane[0])
         throw Error(3, "face / hand extraction needs the frames: with an extractor attached only "
                        "submit_frames / forward_frames are accepted");
 }
@@ -334,7 +334,7 @@ void PoseHip::run_parts(const Slot& sl)
 {
     parts_valid_ = false;
     if (!any_attached()) return;
-    if (!sl.raw.ptr) throw Error(3, "face / hand extraction needs the frames of the collected batch");
+    if (!sl.raw.plane[0]) throw Error(3, "face / hand extraction needs the frames of the collected batch");
     const int n = sl.n;
     const int parts = pose_model(model_).parts;
     part_first_.assign(n + 1, 0);
@@ -357,8 +357,7 @@ void PoseHip::run_parts(const Slot& sl)
         p.kp.assign((size_t)per * total * p.ex->parts() * 3, 0.f);
         const double rect_ms =
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        p.ex->extract(sl.raw.ptr, sl.raw.n, sl.raw.w, sl.raw.h, sl.raw.step, p.rects.data(),
-                      frame_of.data(), total, p.kp.data(), true);
+        p.ex->extract(sl.raw, p.rects.data(), frame_of.data(), total, p.kp.data(), true);
         ++p.batches;
         p.crops += p.ex->crops();
         p.host_ms += rect_ms + p.ex->last_host_ms();
@@ -424,10 +423,11 @@ void PoseHip::set_input(int net_w, int net_h, float dyn, int scale_number, doubl
     scale_gap_ = scale_gap;
 }
 
-void PoseHip::submit_frames(const uint8_t* frames, int n, int w, int h, size_t step)
+void PoseHip::submit_frames(const FrameSource& frames)
 {
+    const int n = frames.n, w = frames.w, h = frames.h;
     OPK_CHECK_ARG(net_ != nullptr, "no network: raw frames need the net");
-    OPK_CHECK_ARG(frames != nullptr && n > 0 && w > 0 && h > 0, "empty frames");
+    OPK_CHECK_ARG(frames.plane[0] != nullptr && n > 0 && w > 0 && h > 0, "empty frames");
     OPK_CHECK_ARG(count_ < 2, "two batches already in flight: collect first");
     OPK_CHECK_ARG(model_ != 6, "BODY_19N (DenseNet normalisation) is not supported");
     double scales[kMaxResizeSources];
@@ -441,7 +441,7 @@ void PoseHip::submit_frames(const uint8_t* frames, int n, int w, int h, size_t s
     for (int i = 0; i < scale_number_; ++i) {
         const int nw = input_hw_[2 * i], nh = input_hw_[2 * i + 1];
         float* x = static_cast<float*>(inputs_[i].get((size_t)n * 3 * nh * nw * sizeof(float)));
-        cvmat_to_input(ctx_, x, frames, n, w, h, step, scales[i], nw, nh, 1, ctx_->stream);
+        cvmat_to_input(ctx_, x, frames, scales[i], nw, nh, 1, ctx_->stream);
         ptrs[i] = x;
         hw[2 * i] = nh;
         hw[2 * i + 1] = nw;
@@ -449,7 +449,7 @@ void PoseHip::submit_frames(const uint8_t* frames, int n, int w, int h, size_t s
     inputs_n_ = n;
     for (int i = 0; i < scale_number_; ++i) map_ratios_[i] = (float)scales[i];
     have_ratios_ = true;
-    cur_raw_ = RawFrames{frames, n, w, h, step};   // kept in the batch's slot (submit_outputs)
+    cur_raw_ = frames;   // a copy, kept in the batch's slot (submit_outputs)
     try {
         if (scale_number_ == 1)
             submit(ptrs[0], n, hw[0], hw[1], w, h);
@@ -457,17 +457,17 @@ void PoseHip::submit_frames(const uint8_t* frames, int n, int w, int h, size_t s
             submit_multi(ptrs, hw, scale_number_, n, w, h);
     } catch (...) {
         have_ratios_ = false;
-        cur_raw_ = RawFrames{};
+        cur_raw_ = FrameSource{};
         throw;
     }
     have_ratios_ = false;
-    cur_raw_ = RawFrames{};
+    cur_raw_ = FrameSource{};
 }
 
-void PoseHip::forward_frames(const uint8_t* frames, int n, int w, int h, size_t step)
+void PoseHip::forward_frames(const FrameSource& frames)
 {
     OPK_CHECK_ARG(count_ == 0, "batches in flight: collect them first");
-    submit_frames(frames, n, w, h, step);
+    submit_frames(frames);
     collect();
 }
 

@@ -52,8 +52,9 @@ public:
     // PoseExtractorCaffe): n BGR uint8 frames [h][step bytes] on device, prepared on the GPU for
     // every scale of set_input(), then the net per scale and the merged post-processing
     void set_input(int net_w, int net_h, float dyn, int scale_number, double scale_gap);
-    void submit_frames(const uint8_t* frames, int n, int w, int h, size_t step);
-    void forward_frames(const uint8_t* frames, int n, int w, int h, size_t step);
+    // (frames: BGR, or NV12 / I420 converted inside the warps)
+    void submit_frames(const FrameSource& frames);
+    void forward_frames(const FrameSource& frames);
     // net input of scale i of the last submit_frames ([n][3][h][w] fp32 device; w/h may be NULL)
     const float* net_input(int i, int* w, int* h) const;
     int collect();                       // frames of the collected batch
@@ -132,11 +133,6 @@ public:
     static int assembly_threads();
 
 private:
-    struct RawFrames {
-        const uint8_t* ptr = nullptr;
-        int n = 0, w = 0, h = 0;
-        size_t step = 0;
-    };
     struct Slot {
         DevBuf peaks, records;
         HostBuf hpeaks, hrecords;
@@ -144,7 +140,8 @@ private:
         int n = 0, H = 0, W = 0;
         float scale = 1.f;
         HeatMap heat{};
-        RawFrames raw{};   // the batch's frames (submit_frames), for the face / hand stages
+        FrameSource raw{};   // a copy of the batch's frame description (submit_frames), for the
+                             // face / hand stages; plane[0] NULL: none
     };
     struct Part {
         KeypointExtractor* ex = nullptr;
@@ -159,7 +156,7 @@ private:
     DevBuf part_dev_[2];
     std::vector<int> part_first_;     // [n + 1]: first person of each frame in the batch's arrays
     bool parts_valid_ = false;
-    RawFrames cur_raw_{};             // set by submit_frames for the submit it makes
+    FrameSource cur_raw_{};           // set by submit_frames for the submit it makes
     bool any_attached() const { return attached(0) || attached(1); }
     void need_frames() const;         // the OPK_ERR_STATE of a submit without frames
     void run_parts(const Slot& sl);

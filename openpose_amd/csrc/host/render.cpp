@@ -13,6 +13,7 @@
 
 #include "../../../include/opk.h"
 #include "context.h"
+#include "input.h"
 
 namespace opk {
 
@@ -154,12 +155,12 @@ namespace {
 
 // ---- the output image (CvMatToOpOutput, OpOutputToCvMat) and the fused batch render -------------
 
-void check_output_sizes(int width, int height, int out_w, int out_h, size_t step, double scale)
+// (the frames' own checks -- format, steps, planes -- are frame_source's, host/input.cpp)
+void check_output_sizes(int width, int height, int out_w, int out_h, double scale)
 {
     // CvMatToOpOutput::createArray's sanity checks (cvMatToOpOutput.cpp:87-90)
     OPK_CHECK_ARG(width > 0 && height > 0, "Input images has 0 area.");
     OPK_CHECK_ARG(out_w > 0 && out_h > 0, "Output resolution has 0 area.");
-    OPK_CHECK_ARG(step == 0 || step >= (size_t)width * 3, "row step shorter than the row");
     OPK_CHECK_ARG(scale > 0 && std::isfinite(scale), "scale must be positive");
 }
 
@@ -171,15 +172,11 @@ void check_cast(int cast)
 
 // resizeFixedAspectRatio (openCvPrivate.cpp:34-53): the copy when nothing changes, else
 // cv::warpAffine(diag(scale)) with the tables of the net-input warp (host/input.cpp)
-FrameWarp frame_warp(Context* ctx, const uint8_t* frames, int width, int height, size_t step,
-                     double scale, int out_w, int out_h)
+FrameWarp frame_warp(Context* ctx, const FrameSource& src, double scale, int out_w, int out_h)
 {
     FrameWarp wp{};
-    wp.src = frames;
-    wp.src_step = step ? step : (size_t)width * 3;
-    wp.sw = width;
-    wp.sh = height;
-    if (scale != 1. || out_w != width || out_h != height) {
+    wp.src = src;
+    if (scale != 1. || out_w != src.w || out_h != src.h) {
         const bool cubic = scale > 1.;
         const auto& ax = ctx->warp_axis_tables(scale, out_w, out_h);
         wp.xtab = ax.x;
@@ -294,25 +291,25 @@ void render_element(int model, int element, int* kind, int* channel)
 }
 
 void render_frames(Context* ctx, uint8_t* dst, size_t dst_step, int out_w, int out_h,
-                   const uint8_t* frames, int n, int width, int height, size_t step, double scale,
-                   const opk_render_layer* layers, int n_layers, int blend_original, int cast,
-                   const float* kp_host, size_t kp_floats, const opk_render_heat* heat,
-                   const HeatMap* lazy)
+                   const FrameSource& src, double scale, const opk_render_layer* layers,
+                   int n_layers, int blend_original, int cast, const float* kp_host,
+                   size_t kp_floats, const opk_render_heat* heat, const HeatMap* lazy)
 {
+    const int n = src.n;
     // everything that does not depend on the frames first, then each frame's counts; device work
     // starts only after the last check
     OPK_CHECK_ARG(n >= 0, "negative frame count");
     OPK_CHECK_ARG(n_layers >= 0 && n_layers <= kRenderMaxLayers, "at most 3 layers");
     OPK_CHECK_ARG(n_layers == 0 || layers, "NULL layers");
     check_cast(cast);
-    check_output_sizes(width, height, out_w, out_h, step, scale);
+    check_output_sizes(src.w, src.h, out_w, out_h, scale);
     OPK_CHECK_ARG(dst_step == 0 || dst_step >= (size_t)out_w * 3, "row step shorter than the row");
     LayerRender lr[kRenderMaxLayers];
     for (int l = 0; l < n_layers; ++l) lr[l] = layer_render(layers[l]);
     RenderFramesHeat heat_args{};
     if (heat) heat_args = heat_layer(*heat, n, blend_original, lazy);
     if (n == 0) return;
-    OPK_CHECK_ARG(dst && frames, "NULL buffer");
+    OPK_CHECK_ARG(dst && src.plane[0], "NULL buffer");
     // prefix offsets of every layer: [n_layers][n + 1]
     std::vector<int> offsets((size_t)n_layers * (n + 1));
     size_t geom_floats = 0, geom_at[kRenderMaxLayers] = {};
@@ -347,7 +344,7 @@ void render_frames(Context* ctx, uint8_t* dst, size_t dst_step, int out_w, int o
     a.w = out_w;
     a.h = out_h;
     a.n = n;
-    a.warp = frame_warp(ctx, frames, width, height, step, scale, out_w, out_h);
+    a.warp = frame_warp(ctx, src, scale, out_w, out_h);
     a.blend = blend_original ? 1 : 0;
     a.cast = cast;
     a.nlayers = n_layers;
@@ -530,21 +527,43 @@ int opk_render_pose_distance(opk_ctx* ctx, float* frame, unsigned width, unsigne
     });
 }
 
+int opk_frames_to_bgr(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, const opk_frames* frames)
+{
+    return opk::guarded_render([&] {
+        OPK_CHECK_ARG(ctx && frames, "NULL argument");
+        const opk::FrameSource src = opk::frame_source(*frames);
+        OPK_CHECK_ARG(src.format != OPK_FRAMES_BGR, "BGR frames: nothing to convert");
+        OPK_CHECK_ARG(src.w > 0 && src.h > 0, "Input images has 0 area.");
+        OPK_CHECK_ARG(dst_step == 0 || dst_step >= (size_t)src.w * 3,
+                      "row step shorter than the row");
+        if (src.n == 0) return;
+        OPK_CHECK_ARG(dst_dev, "NULL buffer");
+        ctx->bind();
+        opk::launch_frames_to_bgr(dst_dev, dst_step ? dst_step : (size_t)src.w * 3, src,
+                                  ctx->stream);
+    });
+}
+
+int opk_cvmat_to_output_fmt(opk_ctx* ctx, float* output_dev, const opk_frames* frames, double scale,
+                            int out_w, int out_h)
+{
+    return opk::guarded_render([&] {
+        OPK_CHECK_ARG(ctx && frames, "NULL argument");
+        const opk::FrameSource src = opk::frame_source(*frames);
+        opk::check_output_sizes(src.w, src.h, out_w, out_h, scale);
+        if (src.n == 0) return;
+        OPK_CHECK_ARG(output_dev && src.plane[0], "NULL buffer");
+        ctx->bind();
+        opk::launch_cvmat_to_output(output_dev, src.n, out_w, out_h,
+                                    opk::frame_warp(ctx, src, scale, out_w, out_h), ctx->stream);
+    });
+}
+
 int opk_cvmat_to_output(opk_ctx* ctx, float* output_dev, const uint8_t* frames_dev, int n, int width,
                         int height, size_t step, double scale, int out_w, int out_h)
 {
-    return opk::guarded_render([&] {
-        OPK_CHECK_ARG(ctx != nullptr, "NULL argument");
-        OPK_CHECK_ARG(n >= 0, "negative frame count");
-        opk::check_output_sizes(width, height, out_w, out_h, step, scale);
-        if (n == 0) return;
-        OPK_CHECK_ARG(output_dev && frames_dev, "NULL buffer");
-        ctx->bind();
-        opk::launch_cvmat_to_output(
-            output_dev, n, out_w, out_h,
-            opk::frame_warp(ctx, frames_dev, width, height, step, scale, out_w, out_h),
-            ctx->stream);
-    });
+    const opk_frames f = opk::bgr_descriptor(frames_dev, n, width, height, step);
+    return opk_cvmat_to_output_fmt(ctx, output_dev, &f, scale, out_w, out_h);
 }
 
 int opk_output_to_cvmat(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, const float* output_dev,
@@ -564,16 +583,37 @@ int opk_output_to_cvmat(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, const f
     });
 }
 
+int opk_render_frames_heat_fmt(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, int out_w,
+                               int out_h, const opk_frames* frames, double scale_input_to_output,
+                               const opk_render_layer* layers, int n_layers, int blend_original,
+                               int cast, const opk_render_heat* heat)
+{
+    return opk::guarded_render([&] {
+        OPK_CHECK_ARG(ctx && frames, "NULL argument");
+        opk::render_frames(ctx, dst_dev, dst_step, out_w, out_h, opk::frame_source(*frames),
+                           scale_input_to_output, layers, n_layers, blend_original, cast, nullptr,
+                           0, heat);
+    });
+}
+
+int opk_render_frames_fmt(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, int out_w, int out_h,
+                          const opk_frames* frames, double scale_input_to_output,
+                          const opk_render_layer* layers, int n_layers, int blend_original, int cast)
+{
+    return opk_render_frames_heat_fmt(ctx, dst_dev, dst_step, out_w, out_h, frames,
+                                      scale_input_to_output, layers, n_layers, blend_original, cast,
+                                      nullptr);
+}
+
 int opk_render_frames(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, int out_w, int out_h,
                       const uint8_t* frames_dev, int n, int width, int height, size_t step,
                       double scale_input_to_output, const opk_render_layer* layers, int n_layers,
                       int blend_original, int cast)
 {
-    return opk::guarded_render([&] {
-        OPK_CHECK_ARG(ctx != nullptr, "NULL argument");
-        opk::render_frames(ctx, dst_dev, dst_step, out_w, out_h, frames_dev, n, width, height,
-                           step, scale_input_to_output, layers, n_layers, blend_original, cast);
-    });
+    const opk_frames f = opk::bgr_descriptor(frames_dev, n, width, height, step);
+    return opk_render_frames_heat_fmt(ctx, dst_dev, dst_step, out_w, out_h, &f,
+                                      scale_input_to_output, layers, n_layers, blend_original, cast,
+                                      nullptr);
 }
 
 int opk_render_frames_heat(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, int out_w, int out_h,
@@ -581,12 +621,10 @@ int opk_render_frames_heat(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, int 
                            double scale_input_to_output, const opk_render_layer* layers,
                            int n_layers, int blend_original, int cast, const opk_render_heat* heat)
 {
-    return opk::guarded_render([&] {
-        OPK_CHECK_ARG(ctx != nullptr, "NULL argument");
-        opk::render_frames(ctx, dst_dev, dst_step, out_w, out_h, frames_dev, n, width, height,
-                           step, scale_input_to_output, layers, n_layers, blend_original, cast,
-                           nullptr, 0, heat);
-    });
+    const opk_frames f = opk::bgr_descriptor(frames_dev, n, width, height, step);
+    return opk_render_frames_heat_fmt(ctx, dst_dev, dst_step, out_w, out_h, &f,
+                                      scale_input_to_output, layers, n_layers, blend_original, cast,
+                                      heat);
 }
 
 int opk_render_element(int pose_model, int element, int* kind, int* channel)

@@ -9,6 +9,8 @@
 // (host/input.cpp) and this kernel only gathers taps and sums integers, so the result is
 // bit-identical to the CPU path by construction.  HBM-bound: 2.76 MB read + 2.90 MB written per
 // 1280x720 -> 656x368 frame.
+// These are the kernels for BGR frames.  NV12 / I420 frames take the same launcher and tables; their
+// kernels, which convert what they read and then sum the same integers, are in yuv.hip.
 #include "kernels.h"
 #include "warp_dev.h"
 #include "../common.h"
@@ -115,20 +117,26 @@ __global__ __launch_bounds__(256) void cvmat_to_input_lds_kernel(
 
 }  // namespace
 
-void launch_cvmat_to_input(float* dst, const uint8_t* src, int n, int sh, int sw, size_t src_step,
-                           int dh, int dw, const int* xtab, const int* ytab, const short* wtab,
-                           int ksize, int normalize, hipStream_t stream, const int* frame_of,
-                           int tab_stride)
+void launch_cvmat_to_input(float* dst, const FrameSource& fs, int n, int dh, int dw,
+                           const int* xtab, const int* ytab, const short* wtab, int ksize,
+                           int normalize, hipStream_t stream, const int* frame_of, int tab_stride)
 {
+    const int sh = fs.h, sw = fs.w;
     OPK_CHECK_ARG(n > 0 && sh > 0 && sw > 0 && dh > 0 && dw > 0, "empty frame");
-    OPK_CHECK_ARG(src_step >= (size_t)sw * 3, "row step shorter than the row");
     OPK_CHECK_ARG(ksize == 2 || ksize == 4, "linear or cubic");
     OPK_CHECK_ARG((long)n * dh < (1L << 31), "too many rows");
+    if (fs.format != kFramesBgr) {   // converted on the way: yuv.hip
+        launch_cvmat_to_input_yuv(dst, fs, n, dh, dw, xtab, ytab, wtab, ksize, normalize, stream,
+                                  frame_of, tab_stride);
+        return;
+    }
+    const uint8_t* src = fs.plane[0];
+    const size_t src_step = fs.step, frame = fs.frame[0];
+    OPK_CHECK_ARG(src_step >= (size_t)sw * 3, "row step shorter than the row");
     const dim3 grid((unsigned)(n * dh));
     const int threads = dw >= 256 ? 256 : (dw >= 128 ? 128 : 64);
     const auto* xt = reinterpret_cast<const int2*>(xtab);
     const auto* yt = reinterpret_cast<const int2*>(ytab);
-    const size_t frame = src_step * sh;
     // staged rows: the column span plus the 16-byte alignment slack, padded to a 4-byte multiple
     const int lds_row = ((sw * 3 + 32) + 15) & ~15;
     const size_t rows_at = ((size_t)dw * 8 + 64 * ksize * ksize + 15) & ~(size_t)15;

@@ -82,16 +82,40 @@ void launch_paf_scores_compact(float* records, int rec_floats, const HeatMap& he
 // LDS bytes a workgroup of either launch stages for this map (0: the sources are read directly)
 size_t paf_staged_bytes(const HeatMap& heat);
 
-// ---- frame -> net input (input.hip) -------------------------------------------------------------
-// src: n BGR uint8 frames [sh][src_step bytes], frame stride src_step*sh; dst [n][3][dh][dw] fp32.
+// ---- frames as the callers hand them over (opk_frames of include/opk.h, resolved) ---------------
+// n uint8 frames of w x h pixels on the device, packed BGR or YUV 4:2:0.  One description serves
+// NV12 and I420: the chroma sample of luma pixel (x, y) of frame f is
+// plane[1 | 2][f * frame[1 | 2] + (y >> 1) * cstep + (x >> 1) * cpix].
+enum FrameFormat { kFramesBgr = 0, kFramesNv12 = 1, kFramesI420 = 2 };
+struct FrameSource {
+    int format;                // FrameFormat
+    int n, w, h;
+    const uint8_t* plane[3];   // frame 0 -- BGR: [0]; YUV: Y, U, V (NV12: V = U + 1)
+    size_t step, cstep;        // row bytes of plane[0] (BGR or luma) and of the chroma rows
+    size_t frame[3];           // bytes from frame f to f + 1 of each plane
+    int cpix;                  // bytes from one chroma sample to the next: 2 NV12, 1 I420
+};
+
+// ---- YUV 4:2:0 -> BGR (yuv.hip; the arithmetic: yuv_dev.h) -------------------------------------
+// dst BGR uint8 [src.n][src.h][dst_step] (only w*3 bytes of a row are written) from NV12 / I420
+void launch_frames_to_bgr(uint8_t* dst, size_t dst_step, const FrameSource& src, hipStream_t stream);
+
+// ---- frame -> net input (input.hip; YUV sources: yuv.hip) ----------------------------------------
+// src: the frames (BGR, or YUV converted on the way: bit for bit the warp of the converted frames);
+// dst [n][3][dh][dw] fp32, n output images.
 // xtab/ytab: per destination column/row {first source tap, 5-bit fraction index}; wtab: the
 // fixed-point 2-D weight table [32*32][ksize*ksize] (host/input.cpp builds all three)
 // frame_of (device, may be NULL): source frame of each output image; tab_stride: distance between
 // the table pairs of consecutive images, in {tap, fraction} entries (0: one shared pair)
-void launch_cvmat_to_input(float* dst, const uint8_t* src, int n, int sh, int sw, size_t src_step,
-                           int dh, int dw, const int* xtab, const int* ytab, const short* wtab,
-                           int ksize, int normalize, hipStream_t stream,
-                           const int* frame_of = nullptr, int tab_stride = 0);
+void launch_cvmat_to_input(float* dst, const FrameSource& src, int n, int dh, int dw,
+                           const int* xtab, const int* ytab, const short* wtab, int ksize,
+                           int normalize, hipStream_t stream, const int* frame_of = nullptr,
+                           int tab_stride = 0);
+// the YUV routes of launch_cvmat_to_input, which checks the arguments (yuv.hip)
+void launch_cvmat_to_input_yuv(float* dst, const FrameSource& src, int n, int dh, int dw,
+                               const int* xtab, const int* ytab, const short* wtab, int ksize,
+                               int normalize, hipStream_t stream, const int* frame_of,
+                               int tab_stride);
 
 // ---- crops of face / hand keypoint extraction (crop.hip) -----------------------------------------
 // peaks [crops][parts][3] = (x, y, value) of the maximum of each of the first `parts` channels of
@@ -129,12 +153,10 @@ void launch_render_keypoints(const RenderKeypointsArgs& a, hipStream_t stream);
 void launch_render_prep(const RenderKeypointsArgs& a, hipStream_t stream);
 
 // ---- output image: CvMatToOpOutput / OpOutputToCvMat and the fused batch render (render.hip) ----
-// The warp of n BGR uint8 frames [sh][src_step] (frame stride src_step * sh) to w x h pixels:
-// ksize 2 / 4 with the tables of launch_cvmat_to_input, or 0 for the plain copy (then w, h = sw, sh)
+// The warp of the frames `src` (BGR, or YUV converted on the way) to w x h pixels: ksize 2 / 4
+// with the tables of launch_cvmat_to_input, or 0 for the plain copy (then w, h = src.w, src.h)
 struct FrameWarp {
-    const uint8_t* src;
-    size_t src_step;
-    int sw, sh;
+    FrameSource src;
     const int* xtab;
     const int* ytab;
     const short* wtab;

@@ -32,6 +32,7 @@
 #include "kernels.h"
 #include "heat_dev.h"
 #include "warp_dev.h"
+#include "yuv_dev.h"
 #include "../common.h"
 
 #include <cmath>
@@ -370,22 +371,25 @@ __global__ __launch_bounds__(256) void render_keypoints_kernel(RenderKeypointsAr
 
 // ---- the output image: CvMatToOpOutput, OpOutputToCvMat and the fused batch render ---------------
 
-// this thread's pixel of frame f as CvMatToOpOutput's warp (or copy, K == 0) gives it
-template <int K>
+// this thread's pixel of frame f as CvMatToOpOutput's warp (or copy, K == 0) gives it; Yuv: the
+// frames are NV12 / I420 and every byte read is converted (yuv_dev.h), the copy included
+template <int K, bool Yuv>
 __device__ __forceinline__ void output_pixel(int u[3], const FrameWarp& wp, int f, int x, int y)
 {
-    const uint8_t* fsrc = wp.src + (size_t)f * wp.src_step * wp.sh;
+    const FrameSource& fs = wp.src;
+    const uint8_t* fsrc = fs.plane[0] + (size_t)f * fs.frame[0];
+    const size_t step = fs.step;
+    // tap row yy: BGR bytes, or the luma and chroma rows
+    auto row_of = [&](int, int yy) {
+        if constexpr (Yuv) return yuv_row(fs, f, yy);
+        else return fsrc + (size_t)yy * step;
+    };
     if constexpr (K == 0) {
-        const uint8_t* p = fsrc + (size_t)y * wp.src_step + (size_t)x * 3;
-        u[0] = p[0];
-        u[1] = p[1];
-        u[2] = p[2];
+        warp_tap(u, row_of(0, y), x);
     } else {
         const int2 xt = reinterpret_cast<const int2*>(wp.xtab)[x];
         const int2 yt = reinterpret_cast<const int2*>(wp.ytab)[y];
-        const size_t step = wp.src_step;
-        warp_pixel<K>(u, yt, xt, warp_weights<K>(wp.wtab, yt.y, xt.y), wp.sh, wp.sw,
-                      [&](int, int yy) { return fsrc + (size_t)yy * step; });
+        warp_pixel<K>(u, yt, xt, warp_weights<K>(wp.wtab, yt.y, xt.y), fs.h, fs.w, row_of);
     }
 }
 
@@ -400,14 +404,14 @@ __device__ __forceinline__ unsigned cast_u8(float v, int cast)
 }
 
 // one thread per output pixel, all three channels
-template <int K>
+template <int K, bool Yuv>
 __global__ __launch_bounds__(256) void cvmat_to_output_kernel(float* __restrict__ dst, int w, int h,
                                                               FrameWarp wp)
 {
     const RenderTile t = render_tile(w, h);
     if (!t.inside) return;
     int u[3];
-    output_pixel<K>(u, wp, blockIdx.z, t.x, t.y);
+    output_pixel<K, Yuv>(u, wp, blockIdx.z, t.x, t.y);
     float* o = dst + 3 * (((size_t)blockIdx.z * h + t.y) * w + t.x);
     o[0] = (float)u[0];
     o[1] = (float)u[1];
@@ -863,7 +867,7 @@ __device__ __forceinline__ void render_heat_pixel(const RenderFramesHeat& H, con
 }
 
 // Heat: the heat layer's mode (kHeatModeNone: the keypoint-only kernel carries none of it)
-template <int K, int Heat>
+template <int K, int Heat, bool Yuv>
 __global__ __launch_bounds__(256) void render_frames_kernel(const RenderFramesArgs a)
 {
     __shared__ unsigned short plist[kRenderMaxPeople];
@@ -875,7 +879,7 @@ __global__ __launch_bounds__(256) void render_frames_kernel(const RenderFramesAr
     float b = 0.f, g = 0.f, r = 0.f;
     if (t.inside && a.blend) {
         int u[3];
-        output_pixel<K>(u, a.warp, f, t.x, t.y);
+        output_pixel<K, Yuv>(u, a.warp, f, t.x, t.y);
         b = (float)u[0];
         g = (float)u[1];
         r = (float)u[2];
@@ -967,10 +971,20 @@ dim3 batch_tiles(int w, int h, int n)
 
 void check_warp(const FrameWarp& wp, int w, int h)
 {
-    OPK_CHECK_ARG(wp.src && wp.sw > 0 && wp.sh > 0, "empty frame");
-    OPK_CHECK_ARG(wp.src_step >= (size_t)wp.sw * 3, "row step shorter than the row");
+    const FrameSource& fs = wp.src;
+    OPK_CHECK_ARG(fs.plane[0] && fs.w > 0 && fs.h > 0, "empty frame");
+    if (fs.format == kFramesBgr) {
+        OPK_CHECK_ARG(fs.step >= (size_t)fs.w * 3, "row step shorter than the row");
+    } else {
+        OPK_CHECK_ARG(fs.format == kFramesNv12 || fs.format == kFramesI420, "unknown frame format");
+        OPK_CHECK_ARG(fs.w % 2 == 0 && fs.h % 2 == 0, "YUV 4:2:0 frames have even width and height");
+        OPK_CHECK_ARG(fs.plane[1] && fs.plane[2], "NULL plane");
+        OPK_CHECK_ARG(fs.cpix == (fs.format == kFramesNv12 ? 2 : 1), "chroma sample stride");
+        OPK_CHECK_ARG(fs.step >= (size_t)fs.w && fs.cstep >= (size_t)(fs.w / 2) * fs.cpix,
+                      "row step shorter than the row");
+    }
     OPK_CHECK_ARG(wp.ksize == 0 || wp.ksize == 2 || wp.ksize == 4, "copy, linear or cubic");
-    OPK_CHECK_ARG(wp.ksize != 0 || (w == wp.sw && h == wp.sh), "a copy keeps the size");
+    OPK_CHECK_ARG(wp.ksize != 0 || (w == fs.w && h == fs.h), "a copy keeps the size");
     OPK_CHECK_ARG(wp.ksize == 0 || (wp.xtab && wp.ytab && wp.wtab), "NULL warp table");
 }
 
@@ -982,12 +996,22 @@ void launch_cvmat_to_output(float* dst, int n, int w, int h, const FrameWarp& wp
     OPK_CHECK_ARG(dst && n > 0 && w > 0 && h > 0, "empty output image");
     check_warp(wp, w, h);
     const dim3 grid = batch_tiles(w, h, n), block(kTileW * kTileH);
+#define OPK_LAUNCH_OUTPUT(K)                                                                     \
+    do {                                                                                         \
+        if (wp.src.format == kFramesBgr)                                                         \
+            hipLaunchKernelGGL((cvmat_to_output_kernel<K, false>), grid, block, 0, stream, dst, w, \
+                               h, wp);                                                           \
+        else                                                                                     \
+            hipLaunchKernelGGL((cvmat_to_output_kernel<K, true>), grid, block, 0, stream, dst, w,  \
+                               h, wp);                                                           \
+    } while (0)
     if (wp.ksize == 0)
-        hipLaunchKernelGGL(cvmat_to_output_kernel<0>, grid, block, 0, stream, dst, w, h, wp);
+        OPK_LAUNCH_OUTPUT(0);
     else if (wp.ksize == 2)
-        hipLaunchKernelGGL(cvmat_to_output_kernel<2>, grid, block, 0, stream, dst, w, h, wp);
+        OPK_LAUNCH_OUTPUT(2);
     else
-        hipLaunchKernelGGL(cvmat_to_output_kernel<4>, grid, block, 0, stream, dst, w, h, wp);
+        OPK_LAUNCH_OUTPUT(4);
+#undef OPK_LAUNCH_OUTPUT
     OPK_LAUNCH_CHECK();
 }
 
@@ -1050,8 +1074,13 @@ void launch_render_frames(const RenderFramesArgs& args, hipStream_t stream)
                    render_heat_staged(H.kind == kHeatPafs && H.count == 1 ? kHeatPaf : H.kind, H.scale);
     }
     const dim3 grid = batch_tiles(a.w, a.h, a.n), block(kTileW * kTileH);
-#define OPK_LAUNCH_FRAMES_MODE(K, M) \
-    hipLaunchKernelGGL((render_frames_kernel<K, M>), grid, block, 0, stream, a)
+#define OPK_LAUNCH_FRAMES_MODE(K, M)                                                           \
+    do {                                                                                       \
+        if (a.warp.src.format == kFramesBgr)                                                   \
+            hipLaunchKernelGGL((render_frames_kernel<K, M, false>), grid, block, 0, stream, a); \
+        else                                                                                   \
+            hipLaunchKernelGGL((render_frames_kernel<K, M, true>), grid, block, 0, stream, a);  \
+    } while (0)
 #define OPK_LAUNCH_FRAMES(K)                                                                       \
     do {                                                                                           \
         if (!heat)                                                                                 \

@@ -18,9 +18,19 @@ __device__ __forceinline__ const short* warp_weights(const short* wtab, int yfra
     return wtab + (yfrac * 32 + xfrac) * K * K;
 }
 
+// pixel xx of a row of packed BGR bytes (a YUV row's fetch: yuv_dev.h)
+__device__ __forceinline__ void warp_tap(int c[3], const uint8_t* row, int xx)
+{
+    const uint8_t* p = row + (size_t)xx * 3;
+    c[0] = p[0];
+    c[1] = p[1];
+    c[2] = p[2];
+}
+
 // u[c] = saturate_cast<uchar>((sum of taps * weights + 2^14) >> 15) of the BGR pixel whose first
-// tap is (xt.x, yt.x); taps outside the sh x sw source read 0 (constant border).  row_of(ky, yy)
-// returns tap row yy's bytes addressed by source column * 3 (called for rows inside the image and,
+// tap is (xt.x, yt.x); taps outside the sh x sw source read 0 (constant border: BGR 0 whatever the
+// source format).  row_of(ky, yy) returns tap row yy as something warp_tap reads a pixel from --
+// BGR bytes addressed by source column * 3, or a YuvRow -- (called for rows inside the image and,
 // with yy = 0, for rows outside it, whose taps are never read).
 template <int K, class RowOf>
 __device__ __forceinline__ void warp_pixel(int u[3], int2 yt, int2 xt, const short* w, int sh,
@@ -31,16 +41,17 @@ __device__ __forceinline__ void warp_pixel(int u[3], int2 yt, int2 xt, const sho
     for (int ky = 0; ky < K; ++ky) {
         const int yy = yt.x + ky;
         const bool yin = yy >= 0 && yy < sh;
-        const uint8_t* row = row_of(ky, yin ? yy : 0);
+        const auto row = row_of(ky, yin ? yy : 0);
 #pragma unroll
         for (int kx = 0; kx < K; ++kx) {
             const int xx = xt.x + kx;
             const int wk = w[ky * K + kx];
             if (yin && xx >= 0 && xx < sw) {   // constant border: outside taps read 0
-                const uint8_t* p = row + (size_t)xx * 3;
-                acc[0] += (int)p[0] * wk;
-                acc[1] += (int)p[1] * wk;
-                acc[2] += (int)p[2] * wk;
+                int c[3];
+                warp_tap(c, row, xx);
+                acc[0] += c[0] * wk;
+                acc[1] += c[1] * wk;
+                acc[2] += c[2] * wk;
             }
         }
     }
