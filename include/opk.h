@@ -298,6 +298,42 @@ int opk_frames_to_bgr(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, const opk
 int opk_cvmat_to_input_fmt(opk_ctx* ctx, float* input_dev, const opk_frames* frames, double scale,
                            int net_w, int net_h, int normalize);
 
+/* ---- Frames out as the encoders take them: the other direction, BGR -> NV12 / I420.
+ *
+ * The conversion is the arithmetic of OpenCV's cvtColor(COLOR_BGR2YUV_I420): BT.601 limited range
+ * in 20-bit fixed point.  In int32, `>>` arithmetic:
+ *      Y = (269484*R + 528482*G + 102760*B + (1<<19) + (16<<20))   >> 20    every pixel
+ *      U = (-155188*R - 305135*G + 460324*B + (1<<19) + (128<<20)) >> 20    of the block's top-left
+ *      V = (460324*R - 385875*G -  74448*B + (1<<19) + (128<<20))  >> 20    pixel (even x, even y);
+ *                                                                           no averaging
+ * NV12 is the same U and V, interleaved with U first (OpenCV's converter has no two-plane target:
+ * for NV12 this text is the whole definition).  For every (B, G, R) each sum is non-negative and
+ * below 2^31, Y lies in [16, 235] and U, V in [16, 240]: there is no clamp.  Black gives (Y, U, V)
+ * = (16, 128, 128), white (235, 128, 128), blue (41, 240, 110), green (145, 54, 34), red
+ * (82, 90, 240).
+ *
+ * ONE DEFINITION: with an NV12 / I420 destination every `_to` function below writes, bit for bit,
+ * opk_bgr_to_frames of the bytes its BGR-out twin writes for the same arguments -- the render
+ * converts in its store epilogue and writes no BGR image; with a BGR destination it writes exactly
+ * the twin's bytes.  Only the samples are written: row padding and the bytes between frames keep
+ * their values.
+ *
+ * opk_frames_out is opk_frames with writable planes and the same defaults for 0; width, height are
+ * the drawn images' out_w, out_h.  OPK_ERR_ARG, before any device work: every descriptor error of
+ * opk_frames; n differing from the source's; destination planes that overlap each other, another
+ * frame of themselves, or the source frames (one byte range per plane and frame, from its first
+ * sample to its last). */
+typedef struct opk_frames_out {
+    int format, n, width, height;
+    uint8_t* plane[3];
+    size_t step[3];
+    size_t frame_bytes[3];
+} opk_frames_out;
+/* BGR frames -> NV12 / I420, the inverse direction of opk_frames_to_bgr, enqueued on the context's
+ * stream.  A non-BGR source, a BGR destination and a destination of another width or height are
+ * OPK_ERR_ARG; n == 0 succeeds without device work. */
+int opk_bgr_to_frames(opk_ctx* ctx, const opk_frames_out* dst, const opk_frames* bgr_src);
+
 /* Kernel-variant switches (no reference counterpart; A/B tests and tuning only): key = one of
  * "CONV3_SMALL", "CONV3_W16", "CONV3_PERSIST", "CONV3_WIDE", "CONV3P_ASMR", "CONV3P_WIDE",
  * "CONV3P_PRIO", "CONV3W", "CONV1_TILE", "CONV1_N64W16", "CONV1_FUSED", "CONV3S_MAX" (read when a
@@ -818,7 +854,8 @@ int opk_pose_render_frames(opk_pose* pose, uint8_t* dst_dev, size_t dst_step, in
                            const uint8_t* frames_dev, int n, int width, int height, size_t step,
                            double scale_input_to_output, float render_threshold, float alpha,
                            int googly_eyes, int blend_original, int cast);
-/* The same on opk_frames descriptors (see opk_frames); the drawn images stay BGR uint8. */
+/* The same on opk_frames descriptors (see opk_frames); the drawn images stay BGR uint8 (NV12 /
+ * I420 out: opk_render_frames_to, opk_pose_render_frames_to below). */
 int opk_render_frames_fmt(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, int out_w, int out_h,
                           const opk_frames* frames, double scale_input_to_output,
                           const opk_render_layer* layers, int n_layers, int blend_original,
@@ -911,6 +948,22 @@ int opk_pose_render_frames_element_fmt(opk_pose* pose, uint8_t* dst_dev, size_t 
                                        float render_threshold, float alpha_keypoint,
                                        float alpha_heatmap, int googly_eyes, int blend_original,
                                        int cast);
+
+/* The drawn frames into an opk_frames_out destination -- BGR, NV12 or I420 (see opk_frames_out:
+ * out_w, out_h are dst->width, dst->height; the YUV samples are opk_bgr_to_frames of the BGR
+ * call's bytes, converted in the render's store epilogue).  Every argument and state error of the
+ * call being wrapped keeps its code and text.
+ * opk_render_frames_to: opk_render_frames_heat_fmt (heat NULL: opk_render_frames_fmt).
+ * opk_pose_render_frames_to: opk_pose_render_frames_element_fmt; with part_params = {face_threshold,
+ *   face_alpha, hand_threshold, hand_alpha} opk_pose_render_frames_parts_fmt with alpha_keypoint as
+ *   its alpha (element must then be 0). */
+int opk_render_frames_to(opk_ctx* ctx, const opk_frames_out* dst, const opk_frames* frames,
+                         double scale_input_to_output, const opk_render_layer* layers, int n_layers,
+                         int blend_original, int cast, const opk_render_heat* heat);
+int opk_pose_render_frames_to(opk_pose* pose, const opk_frames_out* dst, const opk_frames* frames,
+                              double scale_input_to_output, int element, float render_threshold,
+                              float alpha_keypoint, float alpha_heatmap, int googly_eyes,
+                              int blend_original, int cast, const float* part_params);
 
 #ifdef __cplusplus
 }

@@ -165,6 +165,10 @@ _SIGS = {
                                                 _f, _i, _i, _i]),
     "opk_pose_render_frames_element": (_i, [_p, _p, _c.c_size_t, _i, _i, _p, _i, _i, _i,
                                             _c.c_size_t, _d, _i, _f, _f, _f, _i, _i, _i]),
+    # frames out: an opk_frames_out destination (FramesOutStruct), BGR, NV12 or I420
+    "opk_bgr_to_frames": (_i, [_p, _p, _p]),
+    "opk_render_frames_to": (_i, [_p, _p, _p, _d, _p, _i, _i, _i, _p]),
+    "opk_pose_render_frames_to": (_i, [_p, _p, _p, _d, _i, _f, _f, _f, _i, _i, _i, _fp]),
 }
 
 
@@ -172,6 +176,11 @@ class FramesStruct(ctypes.Structure):
     """opk_frames (include/opk.h)."""
     _fields_ = [("format", _i), ("n", _i), ("width", _i), ("height", _i), ("plane", _p * 3),
                 ("step", _c.c_size_t * 3), ("frame_bytes", _c.c_size_t * 3)]
+
+
+class FramesOutStruct(ctypes.Structure):
+    """opk_frames_out (include/opk.h): opk_frames with writable planes."""
+    _fields_ = list(FramesStruct._fields_)
 
 
 class RenderHeatStruct(ctypes.Structure):

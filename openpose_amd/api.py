@@ -88,6 +88,19 @@ def _ptr(t):
 
 
 FRAMES_BGR, FRAMES_NV12, FRAMES_I420 = 0, 1, 2   # opk_frames.format (OPK_FRAMES_*)
+_FORMAT_NAMES = {"nv12": FRAMES_NV12, "i420": FRAMES_I420}
+
+
+def _frames_out(out, out_format, n, oh, ow, device):
+    """The Frames destination of a render call, or None for the tensor path: `out` when it is a
+    Frames, else fresh frames of out_format ("nv12" | "i420")."""
+    if isinstance(out, Frames):
+        assert out_format is None or _FORMAT_NAMES.get(out_format, out_format) == out.format
+        return out
+    if out_format is None:
+        return None
+    assert out is None, "out_format allocates the destination; pass a Frames as out instead"
+    return Frames.empty(out_format, n, oh, ow, device)
 
 
 class Frames:
@@ -135,9 +148,49 @@ class Frames:
             t = t.as_strided((n, h, w * 3), (t.stride(0), t.stride(1), 1))
         return cls(FRAMES_BGR, [cls._plane(t, n, h, w * 3, "bgr")], n, w, h)
 
+    @classmethod
+    def empty_nv12(cls, n, h, w, device="cuda"):
+        """Uninitialised NV12 frames to draw or convert into: y [n, h, w], uv [n, h / 2, w]."""
+        assert w % 2 == 0 and h % 2 == 0, "YUV 4:2:0 frames need an even width and height"
+        return cls.nv12(torch.empty((n, h, w), dtype=torch.uint8, device=device),
+                        torch.empty((n, h // 2, w), dtype=torch.uint8, device=device))
+
+    @classmethod
+    def empty_i420(cls, n, h, w, device="cuda"):
+        """Uninitialised I420 frames: y [n, h, w], u and v [n, h / 2, w / 2]."""
+        assert w % 2 == 0 and h % 2 == 0, "YUV 4:2:0 frames need an even width and height"
+        return cls.i420(torch.empty((n, h, w), dtype=torch.uint8, device=device),
+                        torch.empty((n, h // 2, w // 2), dtype=torch.uint8, device=device),
+                        torch.empty((n, h // 2, w // 2), dtype=torch.uint8, device=device))
+
+    @classmethod
+    def empty(cls, fmt, n, h, w, device="cuda"):
+        """empty_nv12 / empty_i420 by name ("nv12" | "i420") or FRAMES_* value."""
+        fmt = _FORMAT_NAMES.get(fmt, fmt)
+        if fmt not in (FRAMES_NV12, FRAMES_I420):
+            raise ValueError('out_format: "nv12" or "i420"')
+        return (cls.empty_nv12 if fmt == FRAMES_NV12 else cls.empty_i420)(n, h, w, device)
+
+    @classmethod
+    def from_bgr(cls, ctx, t, fmt, out=None):
+        """opk_bgr_to_frames: the BGR frames t ([n, h, w, 3] uint8 CUDA, or a BGR Frames) as NV12 or
+        I420 (fmt "nv12" | "i420"), into the Frames `out` if given (then fmt may be None)."""
+        src = t if isinstance(t, Frames) else cls.bgr(t)
+        if out is None:
+            out = cls.empty(fmt, src.n, src.height, src.width, src.device)
+        s, d = src.struct(), out.struct_out()
+        check(ctx.L.opk_bgr_to_frames(ctx.h, ctypes.byref(d), ctypes.byref(s)))
+        return out
+
     @property
     def device(self):
         return self.planes[0].device
+
+    def struct_out(self):
+        """The opk_frames_out descriptor of these frames as a destination."""
+        s, d = self.struct(), _lib.FramesOutStruct()
+        ctypes.memmove(ctypes.byref(d), ctypes.byref(s), ctypes.sizeof(s))
+        return d
 
     def struct(self):
         """The opk_frames descriptor (a _lib.FramesStruct; the planes stay owned by self)."""
@@ -390,11 +443,14 @@ class Context:
         return out
 
     def render_frames(self, frames, layers, scale=1.0, out_size=None, blend_original=True,
-                      cast=CAST_CPU, out=None, heat=None):
+                      cast=CAST_CPU, out=None, heat=None, out_format=None):
         """CvMatToOpOutput -> the heat layer (a RenderHeat), if any -> the keypoint layers in
         order -> OpOutputToCvMat in one kernel: frames [n, h, w, 3] uint8 BGR (CUDA), layers a
         list of RenderLayer -> uint8 [n, out_h, out_w, 3] (or into the rows of `out`, uint8
-        [n, out_h, row bytes]).  frames may be a Frames (BGR, NV12 or I420)."""
+        [n, out_h, row bytes]).  frames may be a Frames (BGR, NV12 or I420).
+        Frames out: with a Frames as `out` (BGR, NV12 or I420), or out_format="nv12" | "i420",
+        the drawn frames go there (opk_render_frames_to: Frames.from_bgr of the tensor result, bit
+        for bit, converted inside the render) and that Frames is returned."""
         fs = frames.struct() if isinstance(frames, Frames) else None
         if fs is not None:
             n, h, w = frames.n, frames.height, frames.width
@@ -402,7 +458,8 @@ class Context:
             n, h, w, c = frames.shape
             assert c == 3 and frames.dtype == torch.uint8
         ow, oh = out_size if out_size is not None else (w, h)
-        if out is None:
+        dest = _frames_out(out, out_format, n, oh, ow, frames.device)
+        if dest is None and out is None:
             out = torch.empty((n, max(oh, 0), max(ow, 0), 3), dtype=torch.uint8,
                               device=frames.device)
         arr = (_lib.RenderLayerStruct * max(len(layers), 1))()
@@ -423,6 +480,15 @@ class Context:
             s.keypoints_dev = None if l.keypoints is None else _ptr(l.keypoints)
             s.counts_host = counts
             s.render_threshold, s.alpha, s.googly_eyes = l.threshold, l.alpha, int(l.googly_eyes)
+        if dest is not None:
+            hs = None if heat is None else self._heat_struct(heat, n)
+            if fs is None:
+                fs = Frames.bgr(frames).struct()
+            ds = dest.struct_out()
+            check(self.L.opk_render_frames_to(self.h, ctypes.byref(ds), ctypes.byref(fs),
+                                              float(scale), arr, len(layers), int(blend_original),
+                                              cast, None if hs is None else ctypes.byref(hs)))
+            return dest
         if heat is None and fs is not None:
             check(self.L.opk_render_frames_fmt(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow,
                                                oh, ctypes.byref(fs), float(scale), arr,
@@ -433,14 +499,7 @@ class Context:
                                            _ptr(frames), n, w, h, w * 3, float(scale), arr,
                                            len(layers), int(blend_original), cast))
             return out
-        hs = _lib.RenderHeatStruct()
-        hs.kind, hs.pose_model, hs.channel = heat.kind, heat.pose_model, heat.channel
-        if heat.heat is not None:
-            assert heat.heat.dtype == torch.float32 and heat.heat.dim() == 4
-            assert heat.heat.shape[0] == n, "one heat stack per frame"
-            hs.heat_dev = _ptr(heat.heat)
-            hs.channels, hs.heat_h, hs.heat_w = heat.heat.shape[1:]
-        hs.scale_to_keep_ratio, hs.alpha = heat.scale, heat.alpha
+        hs = self._heat_struct(heat, n)
         if fs is not None:
             check(self.L.opk_render_frames_heat_fmt(self.h, _ptr(out), _row_bytes(out, n, oh, ow),
                                                     ow, oh, ctypes.byref(fs), float(scale), arr,
@@ -452,6 +511,19 @@ class Context:
                                             len(layers), int(blend_original), cast,
                                             ctypes.byref(hs)))
         return out
+
+    @staticmethod
+    def _heat_struct(heat, n):
+        """opk_render_heat of a RenderHeat on n frames."""
+        hs = _lib.RenderHeatStruct()
+        hs.kind, hs.pose_model, hs.channel = heat.kind, heat.pose_model, heat.channel
+        if heat.heat is not None:
+            assert heat.heat.dtype == torch.float32 and heat.heat.dim() == 4
+            assert heat.heat.shape[0] == n, "one heat stack per frame"
+            hs.heat_dev = _ptr(heat.heat)
+            hs.channels, hs.heat_h, hs.heat_w = heat.heat.shape[1:]
+        hs.scale_to_keep_ratio, hs.alpha = heat.scale, heat.alpha
+        return hs
 
     def paf_scores(self, scores, heat, peaks, pose_model=BODY_25, inter_th=CONNECT_INTER_THRESHOLD,
                    inter_min_above=CONNECT_INTER_MIN_ABOVE_THRESHOLD, nms_th=NMS_THRESHOLD):
@@ -1057,7 +1129,7 @@ class PoseExtractor:
     def render_frames(self, frames, scale=1.0, out_size=None, threshold=0.05, alpha=0.6,
                       googly_eyes=False, blend_original=True, cast=CAST_CPU, out=None, element=0,
                       alpha_heatmap=0.7, face=False, hands=False, face_threshold=0.4,
-                      face_alpha=0.6, hand_threshold=0.2, hand_alpha=0.6):
+                      face_alpha=0.6, hand_threshold=0.2, hand_alpha=0.6, out_format=None):
         """The last collected batch drawn on its frames [n, h, w, 3] uint8 BGR (CUDA) ->
         uint8 [n, out_h, out_w, 3]; keypoints are scaled by `scale` (scaleInputToOutput).
         element (--part_to_show, see render_element): 0 the keypoints; any other draws that heat
@@ -1066,7 +1138,9 @@ class PoseExtractor:
         face / hands: also draw the attached extractors' results (attach) as a FACE and a HAND
         layer after the POSE layer (opk_pose_render_frames_parts when the flags name every attached
         extractor; a subset is put together from the accessors and drawn by Context.render_frames,
-        the same bytes).  frames may be a Frames (BGR, NV12 or I420)."""
+        the same bytes).  frames may be a Frames (BGR, NV12 or I420).
+        Frames out: a Frames as `out` (BGR, NV12 or I420), or out_format="nv12" | "i420", takes
+        the drawn frames (opk_pose_render_frames_to) and is returned, as Context.render_frames."""
         fs = frames.struct() if isinstance(frames, Frames) else None
         if fs is not None:
             n, h, w = frames.n, frames.height, frames.width
@@ -1074,14 +1148,30 @@ class PoseExtractor:
             n, h, w, c = frames.shape
             assert c == 3 and frames.dtype == torch.uint8
         ow, oh = out_size if out_size is not None else (w, h)
-        if out is None:
+        dest = _frames_out(out, out_format, n, oh, ow, frames.device)
+        if dest is not None:
+            out = dest
+        elif out is None:
             out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
+        every = False
         if face or hands:
             if element != 0:
                 raise ValueError("face / hand layers are drawn with the keypoints (element 0)")
             if (face and FACE not in self._attached) or (hands and HAND not in self._attached):
                 raise ValueError("no such extractor attached")
             every = bool(face) == (FACE in self._attached) and bool(hands) == (HAND in self._attached)
+        if dest is not None and (every or not (face or hands)):
+            if fs is None:
+                fs = Frames.bgr(frames).struct()
+            ds = dest.struct_out()
+            parts = None
+            if every:
+                parts = (ctypes.c_float * 4)(face_threshold, face_alpha, hand_threshold, hand_alpha)
+            check(self.L.opk_pose_render_frames_to(
+                self.h, ctypes.byref(ds), ctypes.byref(fs), float(scale), int(element), threshold,
+                alpha, alpha_heatmap, int(googly_eyes), int(blend_original), cast, parts))
+            return dest
+        if face or hands:
             if every and fs is not None:
                 check(self.L.opk_pose_render_frames_parts_fmt(
                     self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh, ctypes.byref(fs),

@@ -86,8 +86,9 @@ struct Context {
 // still on the host (opk_pose_render_frames); they are uploaded after the argument checks.
 // heat (may be NULL): the heat layer of opk_render_frames_heat; with `lazy` its values come from
 // that map instead of heat->heat_dev (opk_pose_render_frames_element), whose size fields it sets.
-void render_frames(Context* ctx, uint8_t* dst, size_t dst_step, int out_w, int out_h,
-                   const FrameSource& frames, double scale, const ::opk_render_layer* layers,
+// dst: where the drawn frames go, out_w x out_h = dst.w x dst.h -- bgr_dest() of the BGR entry
+// points, or a checked opk_frames_out (frame_dest(), host/input.h) of the `_to` ones.
+void render_frames(Context* ctx, const FrameDest& dst, const FrameSource& frames, double scale, const ::opk_render_layer* layers,
                    int n_layers, int blend_original, int cast,
                    const float* kp_host = nullptr, size_t kp_floats = 0,
                    const ::opk_render_heat* heat = nullptr, const HeatMap* lazy = nullptr);

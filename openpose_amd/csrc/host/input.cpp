@@ -8,6 +8,7 @@
 // Built with -ffp-contract=off: the tables must round exactly as the CPU build does.
 #include "input.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -220,6 +221,88 @@ FrameSource frame_source(const ::opk_frames& d)
     s.frame[1] = d.frame_bytes[1] ? d.frame_bytes[1] : s.cstep * (h / 2);
     s.frame[2] = nv12 ? s.frame[1] : (d.frame_bytes[2] ? d.frame_bytes[2] : s.cstep * (h / 2));
     return s;
+}
+
+FrameDest frame_dest(const ::opk_frames_out& d)
+{
+    // the same fields with writable planes: the same checks and defaults
+    ::opk_frames in{};
+    in.format = d.format;
+    in.n = d.n;
+    in.width = d.width;
+    in.height = d.height;
+    for (int i = 0; i < 3; ++i) {
+        in.plane[i] = d.plane[i];
+        in.step[i] = d.step[i];
+        in.frame_bytes[i] = d.frame_bytes[i];
+    }
+    const FrameSource s = frame_source(in);
+    FrameDest o{};
+    o.format = s.format;
+    o.n = s.n;
+    o.w = s.w;
+    o.h = s.h;
+    o.step = s.step;
+    o.cstep = s.cstep;
+    o.cpix = s.cpix;
+    for (int i = 0; i < 3; ++i) {
+        o.plane[i] = const_cast<uint8_t*>(s.plane[i]);
+        o.frame[i] = s.frame[i];
+    }
+    return o;
+}
+
+void check_frames_apart(const FrameDest& dst, const FrameSource& src)
+{
+    // every plane of every frame as the byte range [first sample, one past its last]; NV12's pairs
+    // are one plane.  A destination range may meet no other range.
+    struct Range {
+        uintptr_t lo, hi;
+        bool dst;
+    };
+    std::vector<Range> ranges;
+    auto add = [&](const uint8_t* base, size_t frame, size_t step, size_t rows, size_t row, int n,
+                   bool is_dst) {
+        if (!base || rows == 0 || row == 0) return;
+        for (int f = 0; f < n; ++f) {
+            const uintptr_t lo = (uintptr_t)base + (size_t)f * frame;
+            ranges.push_back(Range{lo, lo + (rows - 1) * step + row, is_dst});
+        }
+    };
+    auto planes = [&](int format, const uint8_t* const* plane, const size_t* frame, size_t step,
+                      size_t cstep, int n, int w, int h, bool is_dst) {
+        if (w <= 0 || h <= 0) return;
+        if (format == kFramesBgr) {
+            add(plane[0], frame[0], step, (size_t)h, (size_t)w * 3, n, is_dst);
+            return;
+        }
+        add(plane[0], frame[0], step, (size_t)h, (size_t)w, n, is_dst);
+        if (format == kFramesNv12) {
+            add(plane[1], frame[1], cstep, (size_t)h / 2, (size_t)w, n, is_dst);
+        } else {
+            add(plane[1], frame[1], cstep, (size_t)h / 2, (size_t)w / 2, n, is_dst);
+            add(plane[2], frame[2], cstep, (size_t)h / 2, (size_t)w / 2, n, is_dst);
+        }
+    };
+    const uint8_t* dp[3] = {dst.plane[0], dst.plane[1], dst.plane[2]};
+    planes(dst.format, dp, dst.frame, dst.step, dst.cstep, dst.n, dst.w, dst.h, true);
+    planes(src.format, src.plane, src.frame, src.step, src.cstep, src.n, src.w, src.h, false);
+    std::sort(ranges.begin(), ranges.end(), [](const Range& a, const Range& b) { return a.lo < b.lo; });
+    uintptr_t dst_end = 0, src_end = 0;
+    for (const Range& r : ranges) {
+        OPK_CHECK_ARG(r.lo >= dst_end, r.dst ? "destination planes overlap each other"
+                                             : "destination planes overlap the source frames");
+        OPK_CHECK_ARG(!r.dst || r.lo >= src_end, "destination planes overlap the source frames");
+        (r.dst ? dst_end : src_end) = std::max(r.dst ? dst_end : src_end, r.hi);
+    }
+}
+
+FrameDest frame_dest_for(const ::opk_frames_out& dst, const FrameSource& src)
+{
+    const FrameDest d = frame_dest(dst);
+    OPK_CHECK_ARG(d.n == src.n, "the destination's frame count differs from the source's");
+    check_frames_apart(d, src);
+    return d;
 }
 
 void cvmat_to_input(Context* ctx, float* dst, const FrameSource& src, double scale, int dw, int dh,

@@ -44,6 +44,28 @@ inline ::opk_frames bgr_descriptor(const uint8_t* frames, int n, int width, int 
     return d;
 }
 
+// An opk_frames_out descriptor checked and resolved exactly as frame_source does its twin
+FrameDest frame_dest(const ::opk_frames_out& frames);
+// the BGR destination the pointer-taking render entry points describe: n frames [out_h][step bytes]
+// (step 0 stays 0 here: render_frames checks it against the row and then takes the tight value)
+inline FrameDest bgr_dest(uint8_t* dst, size_t step, int n, int out_w, int out_h)
+{
+    FrameDest d{};
+    d.format = kFramesBgr;
+    d.n = n;
+    d.w = out_w;
+    d.h = out_h;
+    d.plane[0] = dst;
+    d.step = step;
+    return d;
+}
+// OPK_ERR_ARG when a plane of `dst` shares a byte with another of its planes or frames, or with
+// the frames `src` (sample ranges per plane and frame; padding and gaps may interleave)
+void check_frames_apart(const FrameDest& dst, const FrameSource& src);
+// the destination of a `_to` call on the frames `src`: frame_dest's errors, then a frame count that
+// differs from the source's, then check_frames_apart -- all OPK_ERR_ARG before any device work
+FrameDest frame_dest_for(const ::opk_frames_out& dst, const FrameSource& src);
+
 // op::CvMatToOpInput::createArray for one scale (cvMatToOpInput.cpp:63-98), a batch of src.n
 // frames on device (BGR, or NV12 / I420 converted inside the warp: the values of the BGR path on
 // opk_frames_to_bgr's output) -> dst [n][3][dh][dw] fp32 on device

@@ -290,12 +290,12 @@ void render_element(int model, int element, int* kind, int* channel)
     if (channel) *channel = c;
 }
 
-void render_frames(Context* ctx, uint8_t* dst, size_t dst_step, int out_w, int out_h,
-                   const FrameSource& src, double scale, const opk_render_layer* layers,
-                   int n_layers, int blend_original, int cast, const float* kp_host,
-                   size_t kp_floats, const opk_render_heat* heat, const HeatMap* lazy)
+void render_frames(Context* ctx, const FrameDest& dst, const FrameSource& src, double scale,
+                   const opk_render_layer* layers, int n_layers, int blend_original, int cast,
+                   const float* kp_host, size_t kp_floats, const opk_render_heat* heat,
+                   const HeatMap* lazy)
 {
-    const int n = src.n;
+    const int n = src.n, out_w = dst.w, out_h = dst.h;
     // everything that does not depend on the frames first, then each frame's counts; device work
     // starts only after the last check
     OPK_CHECK_ARG(n >= 0, "negative frame count");
@@ -303,13 +303,14 @@ void render_frames(Context* ctx, uint8_t* dst, size_t dst_step, int out_w, int o
     OPK_CHECK_ARG(n_layers == 0 || layers, "NULL layers");
     check_cast(cast);
     check_output_sizes(src.w, src.h, out_w, out_h, scale);
-    OPK_CHECK_ARG(dst_step == 0 || dst_step >= (size_t)out_w * 3, "row step shorter than the row");
+    if (dst.format == kFramesBgr)
+        OPK_CHECK_ARG(dst.step == 0 || dst.step >= (size_t)out_w * 3, "row step shorter than the row");
     LayerRender lr[kRenderMaxLayers];
     for (int l = 0; l < n_layers; ++l) lr[l] = layer_render(layers[l]);
     RenderFramesHeat heat_args{};
     if (heat) heat_args = heat_layer(*heat, n, blend_original, lazy);
     if (n == 0) return;
-    OPK_CHECK_ARG(dst && src.plane[0], "NULL buffer");
+    OPK_CHECK_ARG(dst.plane[0] && src.plane[0], "NULL buffer");
     // prefix offsets of every layer: [n_layers][n + 1]
     std::vector<int> offsets((size_t)n_layers * (n + 1));
     size_t geom_floats = 0, geom_at[kRenderMaxLayers] = {};
@@ -339,8 +340,12 @@ void render_frames(Context* ctx, uint8_t* dst, size_t dst_step, int out_w, int o
 
     ctx->bind();
     RenderFramesArgs a{};
-    a.dst = dst;
-    a.dst_step = dst_step ? dst_step : (size_t)out_w * 3;
+    a.out = dst;
+    a.out.n = n;
+    if (dst.format == kFramesBgr) {   // the defaults of the pointer-taking form
+        if (!a.out.step) a.out.step = (size_t)out_w * 3;
+        if (!a.out.frame[0]) a.out.frame[0] = a.out.step * (size_t)out_h;
+    }
     a.w = out_w;
     a.h = out_h;
     a.n = n;
@@ -544,6 +549,36 @@ int opk_frames_to_bgr(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, const opk
     });
 }
 
+int opk_bgr_to_frames(opk_ctx* ctx, const opk_frames_out* dst, const opk_frames* bgr_src)
+{
+    return opk::guarded_render([&] {
+        OPK_CHECK_ARG(ctx && dst && bgr_src, "NULL argument");
+        const opk::FrameSource src = opk::frame_source(*bgr_src);
+        OPK_CHECK_ARG(src.format == OPK_FRAMES_BGR, "the source frames must be BGR");
+        const opk::FrameDest d = opk::frame_dest_for(*dst, src);
+        OPK_CHECK_ARG(d.format != OPK_FRAMES_BGR, "a BGR destination: nothing to convert");
+        OPK_CHECK_ARG(src.w > 0 && src.h > 0, "Input images has 0 area.");
+        OPK_CHECK_ARG(d.w == src.w && d.h == src.h,
+                      "the destination's width and height differ from the source's");
+        if (src.n == 0) return;
+        OPK_CHECK_ARG(src.plane[0], "NULL buffer");
+        ctx->bind();
+        opk::launch_bgr_to_frames(d, src, ctx->stream);
+    });
+}
+
+int opk_render_frames_to(opk_ctx* ctx, const opk_frames_out* dst, const opk_frames* frames,
+                         double scale_input_to_output, const opk_render_layer* layers, int n_layers,
+                         int blend_original, int cast, const opk_render_heat* heat)
+{
+    return opk::guarded_render([&] {
+        OPK_CHECK_ARG(ctx && dst && frames, "NULL argument");
+        const opk::FrameSource src = opk::frame_source(*frames);
+        opk::render_frames(ctx, opk::frame_dest_for(*dst, src), src, scale_input_to_output, layers,
+                           n_layers, blend_original, cast, nullptr, 0, heat);
+    });
+}
+
 int opk_cvmat_to_output_fmt(opk_ctx* ctx, float* output_dev, const opk_frames* frames, double scale,
                             int out_w, int out_h)
 {
@@ -590,7 +625,8 @@ int opk_render_frames_heat_fmt(opk_ctx* ctx, uint8_t* dst_dev, size_t dst_step, 
 {
     return opk::guarded_render([&] {
         OPK_CHECK_ARG(ctx && frames, "NULL argument");
-        opk::render_frames(ctx, dst_dev, dst_step, out_w, out_h, opk::frame_source(*frames),
+        const opk::FrameSource src = opk::frame_source(*frames);
+        opk::render_frames(ctx, opk::bgr_dest(dst_dev, dst_step, src.n, out_w, out_h), src,
                            scale_input_to_output, layers, n_layers, blend_original, cast, nullptr,
                            0, heat);
     });

@@ -96,9 +96,22 @@ struct FrameSource {
     int cpix;                  // bytes from one chroma sample to the next: 2 NV12, 1 I420
 };
 
+// The same description with writable planes: where drawn or converted frames go (opk_frames_out)
+struct FrameDest {
+    int format;
+    int n, w, h;
+    uint8_t* plane[3];
+    size_t step, cstep;
+    size_t frame[3];
+    int cpix;
+};
+
 // ---- YUV 4:2:0 -> BGR (yuv.hip; the arithmetic: yuv_dev.h) -------------------------------------
 // dst BGR uint8 [src.n][src.h][dst_step] (only w*3 bytes of a row are written) from NV12 / I420
 void launch_frames_to_bgr(uint8_t* dst, size_t dst_step, const FrameSource& src, hipStream_t stream);
+// ---- BGR -> YUV 4:2:0 (yuv.hip; the arithmetic: yuv_out_dev.h) ---------------------------------
+// dst NV12 / I420 (only the samples are written) from the BGR frames src of the same n, w, h
+void launch_bgr_to_frames(const FrameDest& dst, const FrameSource& src, hipStream_t stream);
 
 // ---- frame -> net input (input.hip; YUV sources: yuv.hip) ----------------------------------------
 // src: the frames (BGR, or YUV converted on the way: bit for bit the warp of the converted frames);
@@ -196,12 +209,18 @@ struct RenderFramesHeat {
 // floats of the LDS window a tile's heat values are staged in (the kernel's `items` array)
 constexpr int kRenderHeatWindow = 4096;
 struct RenderFramesArgs {
-    uint8_t* dst;
-    size_t dst_step;
+    // the drawn frames: BGR, or NV12 / I420 converted from the cast bytes in the store epilogue
+    // (yuv_out_dev.h); out.w, out.h, out.n = w, h, n
+    FrameDest out;
     int w, h, n;
     FrameWarp warp;
     int blend, cast, nlayers;
-    int dst_aligned;   // set by the launcher: dst and dst_step are multiples of 4
+    // set by the launcher: every plane base, row step and frame stride of `out` is a multiple of 4
+    int dst_aligned;
+    // set by the launcher: out.plane[0], out.step and out.frame[0] side by side -- what a BGR store
+    // needs in two adjacent scalar loads instead of three scattered ones
+    uint8_t* dst;
+    size_t dst_step, dst_frame;
     RenderFramesLayer layer[kRenderMaxLayers];
     RenderFramesHeat heat;   // kind kHeatNone: no heat layer
 };

@@ -33,6 +33,7 @@
 #include "heat_dev.h"
 #include "warp_dev.h"
 #include "yuv_dev.h"
+#include "yuv_out_dev.h"
 #include "../common.h"
 
 #include <cmath>
@@ -866,8 +867,11 @@ __device__ __forceinline__ void render_heat_pixel(const RenderFramesHeat& H, con
     r = px[2];
 }
 
-// Heat: the heat layer's mode (kHeatModeNone: the keypoint-only kernel carries none of it)
-template <int K, int Heat, bool Yuv>
+// Heat: the heat layer's mode (kHeatModeNone: the keypoint-only kernel carries none of it);
+// YuvOut: an NV12 / I420 destination -- a template parameter, not a branch on a.out.format: with the
+// branch the BGR destination measured 0.9 % slower than before it existed; which of
+// the two YUV layouts is a run-time, grid-uniform choice (a.out.cpix)
+template <int K, int Heat, bool Yuv, bool YuvOut>
 __global__ __launch_bounds__(256) void render_frames_kernel(const RenderFramesArgs a)
 {
     __shared__ unsigned short plist[kRenderMaxPeople];
@@ -899,9 +903,82 @@ __global__ __launch_bounds__(256) void render_frames_kernel(const RenderFramesAr
     }
     // 4. OpOutputToCvMat's cast
     const unsigned cb = cast_u8(b, a.cast), cg = cast_u8(g, a.cast), cr = cast_u8(r, a.cast);
+    const int tx0 = blockIdx.x * kTileW, ty0 = blockIdx.y * kTileH;
+    const int rows = min(kTileH, a.h - ty0), cols = min(kTileW, a.w - tx0);
+    // 5. an NV12 / I420 destination: the cast bytes become samples here (yuv_out_dev.h) -- every
+    //    lane its pixel's luma, the lanes at even (x, y) their block's (U, V); w and h are even, so
+    //    a block lies inside the frame, and the tile, with its top-left
+    if constexpr (YuvOut) {
+        const unsigned Y = bgr_to_y((int)cb, (int)cg, (int)cr);
+        const bool top = ((t.x | t.y) & 1) == 0;
+        const unsigned U = bgr_to_u((int)cb, (int)cg, (int)cr);
+        const unsigned V = bgr_to_v((int)cb, (int)cg, (int)cr);
+        const int cpix = a.out.cpix;
+        if (!a.dst_aligned) {
+            if (t.inside) {
+                const YuvOutRow o = yuv_out_row(a.out, f, t.y);
+                o.y[t.x] = (uint8_t)Y;
+                if (top) {
+                    o.u[(t.x >> 1) * cpix] = (uint8_t)U;
+                    o.v[(t.x >> 1) * cpix] = (uint8_t)V;
+                }
+            }
+            return;
+        }
+        // every plane on 4-byte boundaries (a tile starts at byte 32 * blockIdx.x of its luma and
+        // NV12 chroma rows, 16 * blockIdx.x of its I420 ones): the tile's 8 x 32 luma bytes and
+        // 4 x 32 chroma bytes (NV12: pairs; I420: 16 of U at 256, 16 of V at 320 per row) go through
+        // LDS and leave as 4-byte stores: wave 0 the luma, 8 lanes a row; wave 1 the chroma,
+        // 8 (NV12) or 4 + 4 (I420) lanes a row; what a row has left over as bytes
+        uint8_t* stage = reinterpret_cast<uint8_t*>(items);
+        const int lx = threadIdx.x & (kTileW - 1), ly = threadIdx.x / kTileW;
+        stage[threadIdx.x] = (uint8_t)Y;
+        if (top) {
+            if (cpix == 2) {
+                stage[256 + (ly >> 1) * 32 + lx] = (uint8_t)U;
+                stage[256 + (ly >> 1) * 32 + lx + 1] = (uint8_t)V;
+            } else {
+                stage[256 + (ly >> 1) * 16 + (lx >> 1)] = (uint8_t)U;
+                stage[320 + (ly >> 1) * 16 + (lx >> 1)] = (uint8_t)V;
+            }
+        }
+        __syncthreads();
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (wave > 1) return;
+        uint8_t* d;
+        const uint8_t* s;
+        int left;   // bytes of the row from this lane's first
+        if (wave == 0) {
+            const int row = lane >> 3, o = (lane & 7) * 4;
+            if (row >= rows) return;
+            d = a.out.plane[0] + (size_t)f * a.out.frame[0] + (size_t)(ty0 + row) * a.out.step + tx0 + o;
+            s = stage + row * 32 + o;
+            left = cols - o;
+        } else if (cpix == 2) {
+            const int row = lane >> 3, o = (lane & 7) * 4;
+            if (lane >= 32 || 2 * row >= rows) return;
+            d = a.out.plane[1] + (size_t)f * a.out.frame[1] + (size_t)((ty0 >> 1) + row) * a.out.cstep +
+                tx0 + o;
+            s = stage + 256 + row * 32 + o;
+            left = cols - o;
+        } else {
+            const int p = lane >> 4, row = (lane >> 2) & 3, o = (lane & 3) * 4;   // p: U, V
+            if (lane >= 32 || 2 * row >= rows) return;
+            d = a.out.plane[1 + p] + (size_t)f * a.out.frame[1 + p] +
+                (size_t)((ty0 >> 1) + row) * a.out.cstep + (tx0 >> 1) + o;
+            s = stage + 256 + p * 64 + row * 16 + o;
+            left = (cols >> 1) - o;
+        }
+        if (left >= 4) {
+            *reinterpret_cast<unsigned*>(d) = *reinterpret_cast<const unsigned*>(s);
+        } else {
+            for (int i = 0; i < left; ++i) d[i] = s[i];
+        }
+        return;
+    }
     if (!a.dst_aligned) {
         if (t.inside) {
-            uint8_t* d = a.dst + ((size_t)f * a.h + t.y) * a.dst_step + (size_t)t.x * 3;
+            uint8_t* d = a.dst + (size_t)f * a.dst_frame + (size_t)t.y * a.dst_step + (size_t)t.x * 3;
             d[0] = (uint8_t)cb;
             d[1] = (uint8_t)cg;
             d[2] = (uint8_t)cr;
@@ -917,11 +994,11 @@ __global__ __launch_bounds__(256) void render_frames_kernel(const RenderFramesAr
     mine[1] = (uint8_t)cg;
     mine[2] = (uint8_t)cr;
     __syncthreads();
-    const int tx0 = blockIdx.x * kTileW, ty0 = blockIdx.y * kTileH;
-    const int rows = min(kTileH, a.h - ty0), row_bytes = min(kTileW, a.w - tx0) * 3;
+    const int row_bytes = cols * 3;
     const int row = threadIdx.x / 24, o = (threadIdx.x % 24) * 4;
     if (row < rows && o < row_bytes) {   // row < 8 only for threadIdx.x < 192
-        uint8_t* d = a.dst + ((size_t)f * a.h + ty0 + row) * a.dst_step + (size_t)tx0 * 3 + o;
+        uint8_t* d = a.dst + (size_t)f * a.dst_frame + (size_t)(ty0 + row) * a.dst_step +
+                     (size_t)tx0 * 3 + o;
         const uint8_t* s = stage + row * (kTileW * 3) + o;
         if (o + 4 <= row_bytes) {
             *reinterpret_cast<unsigned*>(d) = *reinterpret_cast<const unsigned*>(s);
@@ -1042,9 +1119,35 @@ void launch_output_to_cvmat(uint8_t* dst, size_t dst_step, const float* src, int
 void launch_render_frames(const RenderFramesArgs& args, hipStream_t stream)
 {
     RenderFramesArgs a = args;
-    a.dst_aligned = (uintptr_t)a.dst % 4 == 0 && a.dst_step % 4 == 0;
-    OPK_CHECK_ARG(a.dst && a.n > 0 && a.w > 0 && a.h > 0, "empty output image");
-    OPK_CHECK_ARG(a.dst_step >= (size_t)a.w * 3, "row step shorter than the row");
+    FrameDest& D = a.out;
+    OPK_CHECK_ARG(D.plane[0] && a.n > 0 && a.w > 0 && a.h > 0, "empty output image");
+    OPK_CHECK_ARG(D.n == a.n && D.w == a.w && D.h == a.h, "destination frame count or size");
+    const bool yuv_out = D.format != kFramesBgr;
+    if (!yuv_out) {
+        OPK_CHECK_ARG(D.step >= (size_t)a.w * 3, "row step shorter than the row");
+        a.dst_aligned = (uintptr_t)D.plane[0] % 4 == 0 && D.step % 4 == 0 && D.frame[0] % 4 == 0;
+    } else {
+        OPK_CHECK_ARG(D.format == kFramesNv12 || D.format == kFramesI420, "unknown frame format");
+        OPK_CHECK_ARG(a.w % 2 == 0 && a.h % 2 == 0, "YUV 4:2:0 frames have even width and height");
+        OPK_CHECK_ARG(D.plane[1] && D.plane[2], "NULL plane");
+        OPK_CHECK_ARG(D.cpix == (D.format == kFramesNv12 ? 2 : 1), "chroma sample stride");
+        OPK_CHECK_ARG(D.step >= (size_t)a.w && D.cstep >= (size_t)(a.w / 2) * D.cpix,
+                      "row step shorter than the row");
+        // (NV12's plane[2] is plane[1] + 1: the pairs are stored through plane[1] alone)
+        a.dst_aligned = (uintptr_t)D.plane[0] % 4 == 0 && D.step % 4 == 0 && D.frame[0] % 4 == 0 &&
+                        (uintptr_t)D.plane[1] % 4 == 0 && D.cstep % 4 == 0 && D.frame[1] % 4 == 0 &&
+                        (D.cpix == 2 || ((uintptr_t)D.plane[2] % 4 == 0 && D.frame[2] % 4 == 0));
+    }
+    a.dst = D.plane[0];
+    a.dst_step = D.step;
+    a.dst_frame = D.frame[0];
+    // the store route in the launch log: a4 = the 4-byte stores from the stage
+    if (!yuv_out)
+        note_launch(a.dst_aligned ? "render_frames<a4>" : "render_frames");
+    else if (D.format == kFramesNv12)
+        note_launch(a.dst_aligned ? "render_frames<a4,nv12>" : "render_frames<nv12>");
+    else
+        note_launch(a.dst_aligned ? "render_frames<a4,i420>" : "render_frames<i420>");
     OPK_CHECK_ARG(a.cast == 0 || a.cast == 1, "unknown cast");
     OPK_CHECK_ARG(a.nlayers >= 0 && a.nlayers <= kRenderMaxLayers, "too many layers");
     for (int l = 0; l < a.nlayers; ++l)
@@ -1074,12 +1177,19 @@ void launch_render_frames(const RenderFramesArgs& args, hipStream_t stream)
                    render_heat_staged(H.kind == kHeatPafs && H.count == 1 ? kHeatPaf : H.kind, H.scale);
     }
     const dim3 grid = batch_tiles(a.w, a.h, a.n), block(kTileW * kTileH);
-#define OPK_LAUNCH_FRAMES_MODE(K, M)                                                           \
-    do {                                                                                       \
-        if (a.warp.src.format == kFramesBgr)                                                   \
-            hipLaunchKernelGGL((render_frames_kernel<K, M, false>), grid, block, 0, stream, a); \
-        else                                                                                   \
-            hipLaunchKernelGGL((render_frames_kernel<K, M, true>), grid, block, 0, stream, a);  \
+#define OPK_LAUNCH_FRAMES_OUT(K, M, Y)                                                             \
+    do {                                                                                           \
+        if (!yuv_out)                                                                              \
+            hipLaunchKernelGGL((render_frames_kernel<K, M, Y, false>), grid, block, 0, stream, a); \
+        else                                                                                       \
+            hipLaunchKernelGGL((render_frames_kernel<K, M, Y, true>), grid, block, 0, stream, a);  \
+    } while (0)
+#define OPK_LAUNCH_FRAMES_MODE(K, M)               \
+    do {                                           \
+        if (a.warp.src.format == kFramesBgr)       \
+            OPK_LAUNCH_FRAMES_OUT(K, M, false);    \
+        else                                       \
+            OPK_LAUNCH_FRAMES_OUT(K, M, true);     \
     } while (0)
 #define OPK_LAUNCH_FRAMES(K)                                                                       \
     do {                                                                                           \
@@ -1098,6 +1208,7 @@ void launch_render_frames(const RenderFramesArgs& args, hipStream_t stream)
         OPK_LAUNCH_FRAMES(2);
     else
         OPK_LAUNCH_FRAMES(4);
+#undef OPK_LAUNCH_FRAMES_OUT
 #undef OPK_LAUNCH_FRAMES_MODE
 #undef OPK_LAUNCH_FRAMES
     OPK_LAUNCH_CHECK();

@@ -1,5 +1,6 @@
 // yuv.hip -- YUV 4:2:0 frames (NV12, I420) as the decoders leave them: the standalone conversion to
-// BGR (opk_frames_to_bgr) and the frame -> net input warp of input.hip reading YUV directly.
+// BGR (opk_frames_to_bgr), the frame -> net input warp of input.hip reading YUV directly, and the
+// standalone conversion back for the encoders (opk_bgr_to_frames; the arithmetic: yuv_out_dev.h).
 //
 // The conversion is the integer arithmetic of yuv_dev.h; the warps convert what they read with it
 // and then sum exactly the integers input.hip sums, so the net input is bit for bit the warp of the
@@ -8,6 +9,7 @@
 #include "kernels.h"
 #include "warp_dev.h"
 #include "yuv_dev.h"
+#include "yuv_out_dev.h"
 #include "../common.h"
 
 namespace opk {
@@ -108,6 +110,89 @@ __global__ __launch_bounds__(256) void yuv420_to_bgr_kernel(uint8_t* __restrict_
         bgr2(d0 + (size_t)x * 3, r0, x);
         bgr2(d1 + (size_t)x * 3, r1, x);
     }
+}
+
+// ---- the standalone conversion back: BGR -> NV12 / I420 (yuv_out_dev.h) ---------------------------
+// The same grid and the same two routes.  V: a lane converts two rows of 16 pixels -- six 16-byte
+// loads, 32 luma samples, and the (U, V) of the eight top-left pixels of its blocks -- and stores
+// two 16-byte luma pieces and one 16-byte piece of interleaved pairs (NV12) or two 8-byte pieces
+// (I420); source rows, every destination row and all frame strides lie on such boundaries.  The
+// columns past the last whole group -- and everything when V is off -- go as 2 x 2 blocks, bytes.
+
+// the 16 pixels of 48 BGR bytes: luma words, and (top) the chroma samples of pixels 0, 2, .. 14
+template <bool Top>
+__device__ __forceinline__ uint4 yuv16(const uint4 q[3], unsigned u[8], unsigned v[8])
+{
+    const uint4 all[3] = {q[0], q[1], q[2]};
+    unsigned y[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int p = 0; p < 16; ++p) {
+        const int b = byte_of(all[(3 * p) >> 4], (3 * p) & 15);
+        const int g = byte_of(all[(3 * p + 1) >> 4], (3 * p + 1) & 15);
+        const int r = byte_of(all[(3 * p + 2) >> 4], (3 * p + 2) & 15);
+        y[p >> 2] |= bgr_to_y(b, g, r) << (8 * (p & 3));
+        if (Top && (p & 1) == 0) {
+            u[p >> 1] = bgr_to_u(b, g, r);
+            v[p >> 1] = bgr_to_v(b, g, r);
+        }
+    }
+    return uint4{y[0], y[1], y[2], y[3]};
+}
+
+// the 2 x 2 block at even column x of rows s0 / s1 (BGR bytes) -> four luma bytes, one (U, V)
+__device__ __forceinline__ void yuv_block(const YuvOutRow& r0, const YuvOutRow& r1,
+                                          const uint8_t* s0, const uint8_t* s1, int x)
+{
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const uint8_t* a = s0 + 3 * (x + i);
+        const uint8_t* b = s1 + 3 * (x + i);
+        r0.y[x + i] = (uint8_t)bgr_to_y(a[0], a[1], a[2]);
+        r1.y[x + i] = (uint8_t)bgr_to_y(b[0], b[1], b[2]);
+    }
+    const uint8_t* a = s0 + 3 * x;
+    const int o = (x >> 1) * r0.cpix;
+    r0.u[o] = (uint8_t)bgr_to_u(a[0], a[1], a[2]);
+    r0.v[o] = (uint8_t)bgr_to_v(a[0], a[1], a[2]);
+}
+
+template <bool V>
+__global__ __launch_bounds__(256) void bgr_to_yuv420_kernel(FrameDest dst, FrameSource fs)
+{
+    const int f = blockIdx.z, y0 = 2 * blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const uint8_t* s0 = fs.plane[0] + (size_t)f * fs.frame[0] + (size_t)y0 * fs.step;
+    const uint8_t* s1 = s0 + fs.step;
+    const YuvOutRow r0 = yuv_out_row(dst, f, y0), r1 = yuv_out_row(dst, f, y0 + 1);
+    int x = V ? 16 * i : 2 * i;
+    if (x >= fs.w) return;
+    if (V && x + 16 <= fs.w) {
+        unsigned u[8], v[8];
+        const uint4* q0 = reinterpret_cast<const uint4*>(s0 + (size_t)x * 3);
+        const uint4* q1 = reinterpret_cast<const uint4*>(s1 + (size_t)x * 3);
+        const uint4 a[3] = {q0[0], q0[1], q0[2]}, b[3] = {q1[0], q1[1], q1[2]};
+        *reinterpret_cast<uint4*>(r0.y + x) = yuv16<true>(a, u, v);
+        *reinterpret_cast<uint4*>(r1.y + x) = yuv16<false>(b, u, v);
+        if (dst.cpix == 2) {
+            unsigned w[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                w[k] = u[2 * k] | v[2 * k] << 8 | u[2 * k + 1] << 16 | v[2 * k + 1] << 24;
+            *reinterpret_cast<uint4*>(r0.u + x) = uint4{w[0], w[1], w[2], w[3]};
+        } else {
+            unsigned wu[2], wv[2];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                wu[k] = u[4 * k] | u[4 * k + 1] << 8 | u[4 * k + 2] << 16 | u[4 * k + 3] << 24;
+                wv[k] = v[4 * k] | v[4 * k + 1] << 8 | v[4 * k + 2] << 16 | v[4 * k + 3] << 24;
+            }
+            *reinterpret_cast<uint2*>(r0.u + (x >> 1)) = uint2{wu[0], wu[1]};
+            *reinterpret_cast<uint2*>(r0.v + (x >> 1)) = uint2{wv[0], wv[1]};
+        }
+        return;
+    }
+    const int end = V ? fs.w : x + 2;   // (w is even)
+    for (; x < end; x += 2) yuv_block(r0, r1, s0, s1, x);
 }
 
 // ---- the warp, direct: input.hip's cvmat_to_input_kernel converting every tap it reads -----------
@@ -250,6 +335,42 @@ void launch_frames_to_bgr(uint8_t* dst, size_t dst_step, const FrameSource& fs, 
         note_launch("yuv420_to_bgr");
         hipLaunchKernelGGL(yuv420_to_bgr_kernel<false>, grid, dim3(256), 0, stream, dst, dst_step,
                            fs);
+    }
+    OPK_LAUNCH_CHECK();
+}
+
+void launch_bgr_to_frames(const FrameDest& dst, const FrameSource& fs, hipStream_t stream)
+{
+    OPK_CHECK_ARG(fs.format == kFramesBgr, "the source frames are BGR");
+    OPK_CHECK_ARG(dst.format == kFramesNv12 || dst.format == kFramesI420, "unknown frame format");
+    OPK_CHECK_ARG(fs.n > 0 && fs.w > 0 && fs.h > 0, "empty frame");
+    OPK_CHECK_ARG(dst.n == fs.n && dst.w == fs.w && dst.h == fs.h, "frame count or size differs");
+    OPK_CHECK_ARG(fs.w % 2 == 0 && fs.h % 2 == 0, "YUV 4:2:0 frames have even width and height");
+    OPK_CHECK_ARG(fs.plane[0] && dst.plane[0] && dst.plane[1] && dst.plane[2], "NULL plane");
+    OPK_CHECK_ARG(dst.cpix == (dst.format == kFramesNv12 ? 2 : 1), "chroma sample stride");
+    OPK_CHECK_ARG(fs.step >= (size_t)fs.w * 3 && dst.step >= (size_t)fs.w &&
+                      dst.cstep >= (size_t)(fs.w / 2) * dst.cpix,
+                  "row step shorter than the row");
+    OPK_CHECK_ARG(fs.h / 2 <= 65535 && fs.n <= 65535, "more than 65535 row pairs or frames");
+    // the destination seen as a source has the alignment rules of the 16-pixel pieces
+    FrameSource as{};
+    as.cpix = dst.cpix;
+    as.step = dst.step;
+    as.cstep = dst.cstep;
+    for (int i = 0; i < 3; ++i) {
+        as.plane[i] = dst.plane[i];
+        as.frame[i] = dst.frame[i];
+    }
+    const bool vec = yuv_aligned(as) && (uintptr_t)fs.plane[0] % 16 == 0 && fs.step % 16 == 0 &&
+                     fs.frame[0] % 16 == 0;
+    const int lanes = vec ? (fs.w + 15) / 16 : fs.w / 2;
+    const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)(fs.h / 2), (unsigned)fs.n);
+    if (vec) {
+        note_launch("bgr_to_yuv420<v16>");
+        hipLaunchKernelGGL(bgr_to_yuv420_kernel<true>, grid, dim3(256), 0, stream, dst, fs);
+    } else {
+        note_launch("bgr_to_yuv420");
+        hipLaunchKernelGGL(bgr_to_yuv420_kernel<false>, grid, dim3(256), 0, stream, dst, fs);
     }
     OPK_LAUNCH_CHECK();
 }
