@@ -336,8 +336,8 @@ int opk_bgr_to_frames(opk_ctx* ctx, const opk_frames_out* dst, const opk_frames*
 
 /* Kernel-variant switches (no reference counterpart; A/B tests and tuning only): key = one of
  * "CONV3_SMALL", "CONV3_W16", "CONV3_PERSIST", "CONV3_WIDE", "CONV3P_ASMR", "CONV3P_WIDE",
- * "CONV3P_PRIO", "CONV3W", "CONV1_TILE", "CONV1_N64W16", "CONV1_FUSED", "CONV3S_MAX" (read when a
- * launch is planned);
+ * "CONV3P_PRIO", "CONV3W", "CONV1_TILE", "CONV1_N64W16", "CONV1_FUSED", "CONV3S_MAX", "LK_WAVE" (read
+ * when a launch is planned);
  * reset != 0 removes the key (back to the product default).  Process-wide; the environment is
  * never consulted. */
 int opk_dev_set(const char* key, int value, int reset);
@@ -732,6 +732,144 @@ int opk_pose_part_keypoints(opk_pose* pose, int kind, int frame, float* keypoint
  * Pointers may be NULL. */
 int opk_pose_read_part_times(opk_pose* pose, int kind, int* batches, int* crops, double* host_ms,
                              double* wait_ms);
+
+/* ---- Person ids across frames: op::PersonIdExtractor (--identification;
+ * include/openpose/tracking/personIdExtractor.hpp:11-12, src/openpose/tracking/personIdExtractor.cpp:
+ * 83-290, 429-476) on pyramidal Lucas-Kanade (src/openpose/tracking/pyramidalLK.cpp:272-368,
+ * pyramidalLK.cu).  The reference's constructor throws ("buggy and not working yet",
+ * personIdExtractor.cpp:416) and hands a 3-channel float image to code that indexes one channel, so
+ * there is nothing to run it against: this text is the definition, on a single-channel image
+ * defined here; parity with the reference is by restatement (tests/lk_cases.py) only.
+ * op::PersonTracker (--tracking) is out of scope.
+ * Everything is fp32 with every multiply and add rounded separately and correctly rounded division
+ * and square root, unless integers are named.
+ *
+ * GREY IMAGE.  G = (1868*B + 9617*G + 4899*R + 8192) >> 14 of the BGR pixel, an integer in
+ * [0, 255] taken as a float.  ONE DEFINITION: for NV12 / I420 frames it is the grey of the BGR pixel
+ * opk_frames_to_bgr makes -- not the Y sample; no BGR copy is written.
+ *
+ * PYRAMID, `levels` = 1..3 levels, level 0 the grey image.  Level l+1 of a w x h level has
+ * ((w+1)/2) x ((h+1)/2) pixels; pixel (x, y) is the sum of the taps 1 4 6 4 1 in x, then in y,
+ * around (2x, 2y), times 1/256; an index outside the level is reflected without repeating the edge
+ * (-1 -> 1, -2 -> 2, n -> n-2, again until it is inside; a length-1 axis always gives 0).  Level 1
+ * is k / 2^8 with k < 2^16 and level 2 k / 2^16 with k < 2^24, every partial sum an integer below
+ * 2^24: exact in fp32 in any order.  A fourth level is not, so levels > 3 is OPK_ERR_ARG.
+ * Storage (opk_pyramid_layout): one record per frame -- level 0 uint8, level 1 uint16 (the k above),
+ * level 2 float, each level [h][w] tight and starting on a 16-byte boundary of the record; 1.61 MB
+ * per 1280x720 frame against 4.84 MB all in float.  opk_pyramid_level returns any level as fp32.
+ *
+ * ONE POINT (levels 3, patch 21): (x, y, status) in level-0 pixels, from pyramid I to pyramid J.
+ *   A point whose status is not 0 is returned unchanged (pyramidalLK.cu:41).  A coordinate that is
+ *   not finite or has |c| >= 2^24 gives status 3 and the point unchanged.  Otherwise
+ *   pI = (x * 0.25f, y * 0.25f), pJ = pI, and for l = 2, 1, 0 with w, h the size of level l and
+ *   xi = (int)pI.x, yi = (int)pI.y, xj = (int)pJ.x, yj = (int)pJ.y (toward zero; a value that is
+ *   not inside (-2^30, 2^30), NaN included, counts as outside every level):
+ *     gradient patch: if xi-11 < 0 || xi+11 >= w || yi-11 < 0 || yi+11 >= h every ix, iy is 0;
+ *       otherwise for i, j in -10..10 (i the row):
+ *       ix = (I[yi+i][xi+j+1] - I[yi+i][xi+j-1]) / 2,  iy = (I[yi+i+1][xi+j] - I[yi+i-1][xi+j]) / 2;
+ *     time patch: if (xi, yi) +- 10 leaves I or (xj, yj) +- 10 leaves J every `it` is 0, otherwise
+ *       it = J[yj+i][xj+j] - I[yi+i][xi+j];
+ *     sxx = sum ix*ix, syy = sum iy*iy, sxy = sum ix*iy, sxt = sum ix*it, syt = sum iy*it, each
+ *       accumulated sequentially from 0 in row-major order (i outer, j inner), product rounded, then
+ *       added;
+ *     den = sxx*syy - sxy*sxy; if |den| < 1e-9f the level's status is 3 and pJ stays, otherwise
+ *       pJ.x += ((-1*syy)*sxt + sxy*syt) / den,  pJ.y += ((-1*sxx)*syt + sxt*sxy) / den;
+ *     a non-zero level status becomes the point's status and stays; the later levels still run;
+ *     after levels 2 and 1, pI and pJ are multiplied by 2.
+ *   The result is (pJ, status).  Nothing is read before its bounds test.
+ *
+ * MATCHING (matchLKAndOPGreedy), opk_match_people: entries [n][parts][3] and people [m][parts][3]
+ *   hold (x, y, status); a part is active for a pair when both statuses are 0.
+ *   threshold = max(10.f, distance * (float)sqrt((double)(width*height)) / 960.f).
+ *   Rounds until one assigns nobody: best = 0; for every person without an id, in order, and every
+ *   entry not yet used, in ascending id order: d = sqrtf(dx*dx + dy*dy) of every active part (entry
+ *   minus person), total = their sequential sum, inliers those with d < threshold, score =
+ *   inliers / (float)active (no active part: the pair is skipped); if score == best && score >=
+ *   inlier_ratio the pair joins the round's candidates, else if score > best && score >=
+ *   inlier_ratio it becomes the only candidate and best = score.  The candidates are then taken by
+ *   ascending total (a NaN total last); where the reference leaves the order open (unordered_map
+ *   iteration, an unstable sort) equal totals go by the lower entry id, then the lower person index.
+ *   A candidate whose entry is used is skipped; otherwise the person gets the entry's id -- also a
+ *   person who got one earlier in the round -- and the entry is used.
+ *   Afterwards every person still without an id gets next_id++, in person order.
+ *
+ * TRACKER.  State: next_id (from 0), the previous frame's pyramid, entries {id -> parts x (x, y,
+ *   status), counter}.  Defaults (personIdExtractor.hpp:11-12): confidence 0.1, inlier ratio 0.5,
+ *   distance 30, frames to delete 10.  Per frame, with its keypoints [people][parts][3] (x, y, score):
+ *   1. capture: every person as (x, y, status), status 1 where score < confidence, else 0;
+ *   2. the first frame: every person becomes an entry of its capture with id next_id++, counter 0;
+ *   3. any later frame: every entry, in id order: if (counter++ > frames_to_delete) it is erased,
+ *      otherwise all its points are propagated from the previous pyramid to this frame's;
+ *   4. matching of the entries against the captures (on the first frame too);
+ *   5. every person's entry (its id's) is replaced by its capture, counter 0.
+ *   A frame without people still ages and propagates.  Frames of another size, or people of another
+ *   part count, than the state holds are OPK_ERR_STATE until opk_tracker_reset. */
+typedef struct opk_lk_point {
+    int frame_i, frame_j;   /* pyramids I and J: records of the batch buffer, -1 = the carry record */
+    float x, y;
+    int status;
+} opk_lk_point;
+/* level sizes, byte offsets of the levels in a frame's record, and the record's bytes (any output
+ * may be NULL; the arrays take `levels` entries) */
+int opk_pyramid_layout(int width, int height, int levels, int* level_w, int* level_h,
+                       size_t* level_offset, size_t* frame_bytes);
+/* grey + pyramid of every frame (BGR, NV12, I420; any step; odd sizes for BGR) into pyramid_dev,
+ * frames->n records of opk_pyramid_layout(frames->width, frames->height, levels); enqueued on the
+ * context's stream */
+int opk_pyramid_build(opk_ctx* ctx, void* pyramid_dev, const opk_frames* frames, int levels);
+/* dst_dev float [n][level_h][level_w] = level `level` of n records (tests, debugging) */
+int opk_pyramid_level(opk_ctx* ctx, float* dst_dev, const void* pyramid_dev, int n, int width,
+                      int height, int levels, int level);
+/* One launch over npoints records on the device, updated in place: frame_i / frame_j index the
+ * n_frames records of pyramid_dev (3 levels of width x height), -1 the single record carry_dev (may
+ * be NULL).  A record naming a frame outside them gets status 3 and is not followed.  Enqueued on
+ * the context's stream. */
+int opk_lk_points(opk_ctx* ctx, const void* pyramid_dev, int n_frames, const void* carry_dev,
+                  int width, int height, opk_lk_point* points_dev, int npoints);
+/* MATCHING above, a pure host function (no context): entry_ids_host strictly ascending;
+ * ids_host [people]; *next_id is read and advanced. */
+int opk_match_people(const float* entries_host, const long long* entry_ids_host, int n_entries,
+                     const float* people_host, int people, int parts, float inlier_ratio,
+                     float distance, int width, int height, long long* next_id,
+                     long long* ids_host);
+
+typedef struct opk_tracker opk_tracker;
+int opk_tracker_create(opk_ctx* ctx, float confidence, float inlier_ratio, float distance,
+                       int frames_to_delete, opk_tracker** out);
+int opk_tracker_destroy(opk_tracker* t);
+int opk_tracker_reset(opk_tracker* t);
+/* frames->n frames in order; keypoints_host: their people one frame after the other
+ * [sum(people_per_frame)][parts][3]; ids_host [sum(people_per_frame)].  Any number of calls: the
+ * state carries over, and the ids equal those of the same frames given one at a time.  Between
+ * calls only the last frame's pyramid is kept.  The fresh points of the whole batch -- frame f-1's
+ * people into frame f, the carried frame's into frame 0 -- go in one launch; entries nobody
+ * re-detected are propagated with one small launch per frame that has any.  Synchronous. */
+int opk_tracker_update(opk_tracker* t, const opk_frames* frames, const float* keypoints_host,
+                       const int* people_per_frame, int parts, long long* ids_host);
+/* Measurement hook: while enabled the pyramid and LK launches are bracketed by HIP events; read
+ * returns, since the last read, the updates, their device milliseconds, and the host milliseconds
+ * of capture, bookkeeping and matching (the waits for the device excluded); device_bytes = the
+ * pyramids, the carried frame and the point records held.  Pointers may be NULL. */
+int opk_tracker_set_timing(opk_tracker* t, int enable);
+int opk_tracker_read_times(opk_tracker* t, int* batches, double* pyramid_ms, double* lk_ms,
+                           double* host_ms, size_t* device_bytes);
+/* The tracker as a stage of the pose pipeline, under the rules of opk_pose_attach_extractor: the
+ * tracker must be of the pose extractor's context (OPK_ERR_ARG); a second tracker, and attaching or
+ * detaching with batches in flight, are OPK_ERR_STATE; a tracker destroyed while attached counts as
+ * detached.  While attached the pipeline accepts the raw-frame path only (every other submit /
+ * forward: OPK_ERR_STATE) and the frame-lifetime rule holds.  The pyramid of a batch is queued at its
+ * submit, on the context stream; opk_pose_collect then, after the people assembly and the face /
+ * hand stages, runs LK and the matching of the batch's frames (opk_tracker_update's steps on
+ * opk_pose_keypoints' arrays) on the context stream -- behind the nets of the next batch that an
+ * earlier submit queued. */
+int opk_pose_attach_tracker(opk_pose* pose, opk_tracker* t);
+int opk_pose_detach_tracker(opk_pose* pose);
+/* ids of one collected frame, person order that of opk_pose_keypoints; OPK_ERR_STATE without a
+ * tracker or a batch collected with it */
+int opk_pose_person_ids(opk_pose* pose, int frame, long long* ids_host);
+/* opk_tracker_read_times of the attached tracker */
+int opk_pose_read_track_times(opk_pose* pose, int* batches, double* pyramid_ms, double* lk_ms,
+                              double* host_ms);
 
 /* ---- Measured ceilings (no reference counterpart; SURVEY.md §8d "confirm the vendor peaks"):
  *      dense fp16 MFMA rate of v_mfma_f32_16x16x32_f16 from registers (the conv kernels'

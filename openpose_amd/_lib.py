@@ -169,6 +169,25 @@ _SIGS = {
     "opk_bgr_to_frames": (_i, [_p, _p, _p]),
     "opk_render_frames_to": (_i, [_p, _p, _p, _d, _p, _i, _i, _i, _p]),
     "opk_pose_render_frames_to": (_i, [_p, _p, _p, _d, _i, _f, _f, _f, _i, _i, _i, _fp]),
+    # person ids across frames: pyramid, Lucas-Kanade, matching, tracker
+    "opk_pyramid_layout": (_i, [_i, _i, _i, _ip, _ip, _c.POINTER(_c.c_size_t),
+                                _c.POINTER(_c.c_size_t)]),
+    "opk_pyramid_build": (_i, [_p, _p, _p, _i]),
+    "opk_pyramid_level": (_i, [_p, _p, _p, _i, _i, _i, _i, _i]),
+    "opk_lk_points": (_i, [_p, _p, _i, _p, _i, _i, _p, _i]),
+    "opk_match_people": (_i, [_p, _p, _i, _p, _i, _i, _f, _f, _i, _i, _c.POINTER(_c.c_longlong),
+                              _p]),
+    "opk_tracker_create": (_i, [_p, _f, _f, _f, _i, _c.POINTER(_p)]),
+    "opk_tracker_destroy": (_i, [_p]),
+    "opk_tracker_reset": (_i, [_p]),
+    "opk_tracker_update": (_i, [_p, _p, _p, _p, _i, _p]),
+    "opk_tracker_set_timing": (_i, [_p, _i]),
+    "opk_tracker_read_times": (_i, [_p, _ip, _c.POINTER(_d), _c.POINTER(_d), _c.POINTER(_d),
+                                    _c.POINTER(_c.c_size_t)]),
+    "opk_pose_attach_tracker": (_i, [_p, _p]),
+    "opk_pose_detach_tracker": (_i, [_p]),
+    "opk_pose_person_ids": (_i, [_p, _i, _p]),
+    "opk_pose_read_track_times": (_i, [_p, _ip, _c.POINTER(_d), _c.POINTER(_d), _c.POINTER(_d)]),
 }
 
 

@@ -217,13 +217,13 @@ class Frames:
 
 # Handles still open at interpreter exit (e.g. held by a test traceback) are closed before the HIP
 # runtime's own teardown: poses, then nets, then contexts.
-_LIVE = {"pose": weakref.WeakSet(), "extractor": weakref.WeakSet(), "net": weakref.WeakSet(),
-         "ctx": weakref.WeakSet()}
+_LIVE = {"pose": weakref.WeakSet(), "extractor": weakref.WeakSet(), "tracker": weakref.WeakSet(),
+         "net": weakref.WeakSet(), "ctx": weakref.WeakSet()}
 
 
 @atexit.register
 def _close_live():
-    for kind in ("pose", "extractor", "net", "ctx"):
+    for kind in ("pose", "extractor", "tracker", "net", "ctx"):
         for obj in list(_LIVE[kind]):
             try:
                 obj.close()
@@ -311,6 +311,32 @@ class Context:
         self.h = h
         _LIVE["ctx"].add(self)
         return self
+
+    # ---- person ids across frames -------------------------------------------------------------
+    def pyramid(self, frames, levels=3):
+        """opk_pyramid_build: the grey image and Gaussian pyramid (`levels` 1..3) of every frame --
+        uint8 [n, h, w, 3] BGR (CUDA) or a Frames (BGR, NV12, I420) -- as a Pyramid."""
+        fr = frames if isinstance(frames, Frames) else Frames.bgr(frames)
+        pyr = Pyramid(self, fr.n, fr.width, fr.height, levels, fr.device)
+        s = fr.struct()
+        check(self.L.opk_pyramid_build(self.h, _ptr(pyr.buffer), ctypes.byref(s), levels))
+        return pyr
+
+    def lk_points(self, pyramid, points, carry=None):
+        """opk_lk_points: one pyramidal Lucas-Kanade launch over `points`, a numpy array of LK_POINT
+        records (frame_i, frame_j, x, y, status) addressing the frames of `pyramid` (3 levels) and,
+        as frame -1, the single frame of the Pyramid `carry`.  Returns the updated records."""
+        pts = np.ascontiguousarray(points, LK_POINT)
+        if carry is not None:
+            assert (carry.n, carry.width, carry.height, carry.levels) == (
+                1, pyramid.width, pyramid.height, pyramid.levels)
+        dev = torch.from_numpy(pts.view(np.uint8).reshape(-1).copy()).to(pyramid.buffer.device)
+        check(self.L.opk_lk_points(self.h, _ptr(pyramid.buffer), pyramid.n,
+                                   _ptr(carry.buffer) if carry is not None else None,
+                                   pyramid.width, pyramid.height, _ptr(dev) if pts.size else None,
+                                   pts.size))
+        self.sync()
+        return dev.cpu().numpy().view(LK_POINT).reshape(pts.shape)
 
     # ---- operators ---------------------------------------------------------------------------
     def convert(self, dst, src):
@@ -664,12 +690,16 @@ def save_people_json(path, keypoint_vector, candidates=None, human_readable=Fals
     del keep
 
 
-def datum_keypoint_vector(pose_keypoints, face_keypoints=None, hand_keypoints=(None, None)):
+def datum_keypoint_vector(pose_keypoints, face_keypoints=None, hand_keypoints=(None, None),
+                          person_ids=None):
     """The keypointVector WPeopleJsonSaver builds from a Datum (wPeopleJsonSaver.hpp:75-88):
     person ids (-1 each without a person-id extractor, PoseExtractor::extractIds,
-    poseExtractor.cpp:136-151), the 2-D body / face / hand arrays and the (empty) 3-D ones."""
+    poseExtractor.cpp:136-151; person_ids: a Tracker's), the 2-D body / face / hand arrays and the
+    (empty) 3-D ones."""
     pk = np.asarray(pose_keypoints, np.float32)
     ids = np.full(pk.shape[0], -1, np.float32) if pk.size else None
+    if person_ids is not None and pk.size:
+        ids = np.asarray(person_ids, np.float32)
     return [(ids, "person_id"), (pk, "pose_keypoints_2d"), (face_keypoints, "face_keypoints_2d"),
             (hand_keypoints[0], "hand_left_keypoints_2d"),
             (hand_keypoints[1], "hand_right_keypoints_2d"), (None, "pose_keypoints_3d"),
@@ -732,6 +762,129 @@ def assemble_people(pair_scores, peaks, pose_model=BODY_25, scale=1.0, max_peopl
                                           scale, int(maximize_positives), semantics))
     k = min(n.value, max_people)
     return kp[:k].copy(), ks[:k].copy()
+
+
+# opk_lk_point: one point of Context.lk_points
+LK_POINT = np.dtype([("frame_i", "<i4"), ("frame_j", "<i4"), ("x", "<f4"), ("y", "<f4"),
+                     ("status", "<i4")])
+# op::PersonIdExtractor's defaults (personIdExtractor.hpp:11-12)
+TRACK_CONFIDENCE, TRACK_INLIER_RATIO, TRACK_DISTANCE, TRACK_FRAMES_TO_DELETE = 0.1, 0.5, 30.0, 10
+
+
+def pyramid_layout(width, height, levels=3):
+    """opk_pyramid_layout: dict(sizes=[(w, h)] per level, offsets=[bytes], frame_bytes) of one
+    frame's pyramid record (level 0 uint8, level 1 uint16 = 256 x value, level 2 float32)."""
+    n = max(levels, 1)
+    w, h = (ctypes.c_int * n)(), (ctypes.c_int * n)()
+    at, fb = (ctypes.c_size_t * n)(), ctypes.c_size_t()
+    check(_lib.load().opk_pyramid_layout(width, height, levels, w, h, at, ctypes.byref(fb)))
+    return dict(sizes=[(w[i], h[i]) for i in range(levels)], offsets=[at[i] for i in range(levels)],
+                frame_bytes=fb.value)
+
+
+class Pyramid:
+    """The pyramid records of n frames on the device (Context.pyramid)."""
+
+    def __init__(self, ctx, n, width, height, levels, device="cuda", buffer=None):
+        self.ctx, self.n, self.width, self.height, self.levels = ctx, n, width, height, levels
+        self.layout = pyramid_layout(width, height, levels)
+        fb = self.layout["frame_bytes"]
+        self.buffer = buffer if buffer is not None else torch.empty(max(n * fb, 1), dtype=torch.uint8,
+                                                                    device=device)
+
+    def frame(self, f):
+        """The record of frame f as a one-frame Pyramid sharing this buffer (a carry frame)."""
+        fb = self.layout["frame_bytes"]
+        return Pyramid(self.ctx, 1, self.width, self.height, self.levels,
+                       buffer=self.buffer[f * fb:(f + 1) * fb])
+
+    def level(self, level):
+        """opk_pyramid_level: float32 numpy [n, h, w] of one level."""
+        w, h = self.layout["sizes"][level] if 0 <= level < self.levels else (1, 1)
+        out = torch.empty((self.n, h, w), dtype=torch.float32, device=self.buffer.device)
+        check(self.ctx.L.opk_pyramid_level(self.ctx.h, _ptr(out), _ptr(self.buffer), self.n,
+                                           self.width, self.height, self.levels, level))
+        self.ctx.sync()
+        return out.cpu().numpy()
+
+
+def match_people(entries, entry_ids, people, size, next_id=0, inlier_ratio=TRACK_INLIER_RATIO,
+                 distance=TRACK_DISTANCE):
+    """opk_match_people (matchLKAndOPGreedy; host only): entries [n, parts, 3] and people
+    [m, parts, 3] of (x, y, status), entry_ids ascending, size = (width, height).  Returns
+    (ids int64 [m], next_id)."""
+    people = np.ascontiguousarray(people, np.float32)
+    entries = np.ascontiguousarray(entries, np.float32).reshape(-1, *people.shape[1:])
+    eid = np.ascontiguousarray(entry_ids, np.int64)
+    assert eid.shape == (entries.shape[0],) and people.ndim == 3 and people.shape[2] == 3
+    ids = np.full(people.shape[0], -2, np.int64)
+    nid = ctypes.c_longlong(next_id)
+    check(_lib.load().opk_match_people(
+        entries.ctypes.data_as(ctypes.c_void_p), eid.ctypes.data_as(ctypes.c_void_p),
+        entries.shape[0], people.ctypes.data_as(ctypes.c_void_p), people.shape[0], people.shape[1],
+        inlier_ratio, distance, size[0], size[1], ctypes.byref(nid),
+        ids.ctypes.data_as(ctypes.c_void_p)))
+    return ids, nid.value
+
+
+class Tracker:
+    """Person ids across video frames (op::PersonIdExtractor, --identification): a 3-level pyramid
+    per frame, one Lucas-Kanade step per level around every keypoint of the tracked people, and the
+    reference's greedy match of the propagated people against the new detections."""
+
+    def __init__(self, ctx, confidence=TRACK_CONFIDENCE, inlier_ratio=TRACK_INLIER_RATIO,
+                 distance=TRACK_DISTANCE, frames_to_delete=TRACK_FRAMES_TO_DELETE):
+        self.ctx, self.L = ctx, ctx.L
+        h = ctypes.c_void_p()
+        check(self.L.opk_tracker_create(ctx.h, confidence, inlier_ratio, distance, frames_to_delete,
+                                        ctypes.byref(h)))
+        self.h = h
+        _LIVE["tracker"].add(self)
+
+    def close(self):
+        if self.h:
+            self.L.opk_tracker_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        check(self.L.opk_tracker_reset(self.h))
+
+    def update(self, frames, keypoints_list):
+        """The ids of the people of n consecutive frames: frames uint8 [n, h, w, 3] BGR (CUDA) or a
+        Frames; keypoints_list = per frame [people, parts, 3] (x, y, score).  Returns a list of
+        int64 arrays.  Any number of calls; the state carries over."""
+        fr = frames if isinstance(frames, Frames) else Frames.bgr(frames)
+        assert len(keypoints_list) == fr.n
+        kps = [np.ascontiguousarray(k, np.float32) for k in keypoints_list]
+        parts = max([k.shape[1] for k in kps if k.ndim == 3] + [1])
+        kps = [k.reshape(-1, parts, 3) for k in kps]
+        counts = np.array([k.shape[0] for k in kps], np.int32)
+        flat = np.ascontiguousarray(np.concatenate(kps) if kps else np.zeros((0, parts, 3), np.float32))
+        ids = np.full(int(counts.sum()), -2, np.int64)
+        s = fr.struct()
+        check(self.L.opk_tracker_update(self.h, ctypes.byref(s),
+                                        flat.ctypes.data_as(ctypes.c_void_p),
+                                        counts.ctypes.data_as(ctypes.c_void_p), parts,
+                                        ids.ctypes.data_as(ctypes.c_void_p)))
+        return [a.copy() for a in np.split(ids, np.cumsum(counts)[:-1])] if fr.n else []
+
+    def set_timing(self, on=True):
+        check(self.L.opk_tracker_set_timing(self.h, int(on)))
+
+    def read_times(self):
+        """{batches, pyramid_ms, lk_ms, host_ms, device_bytes} since the last read."""
+        b, p, l, h = ctypes.c_int(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+        m = ctypes.c_size_t(0)
+        check(self.L.opk_tracker_read_times(self.h, ctypes.byref(b), ctypes.byref(p), ctypes.byref(l),
+                                            ctypes.byref(h), ctypes.byref(m)))
+        return {"batches": b.value, "pyramid_ms": p.value, "lk_ms": l.value, "host_ms": h.value,
+                "device_bytes": m.value}
 
 
 class Net:
@@ -929,19 +1082,26 @@ class PoseExtractor:
         self.parts = pose_model_info(pose_model)["parts"]
         self.pose_model = pose_model
         self._attached = {}   # kind -> KeypointExtractor (kept alive while attached)
+        self._tracker = None  # the attached Tracker
 
     def close(self):
         if self.h:
             self.L.opk_pose_destroy(self.h)
             self.h = None
             self._attached = {}
+            self._tracker = None
 
     # ---- face / hand stages (opk_pose_attach_extractor) ---------------------------------------
-    def attach(self, face=None, hands=None):
+    def attach(self, face=None, hands=None, tracker=None):
         """Run these KeypointExtractors (kind FACE / HAND) inside collect(): rectangles from each
         frame's pose keypoints, then the extractor on the batch's frames.  Only forward_frames /
         submit_frames are accepted while one is attached, and a submitted batch's frames must stay
-        unchanged until it is collected."""
+        unchanged until it is collected.
+        tracker: a Tracker under the same rules (opk_pose_attach_tracker): the batch's pyramid is
+        queued at submit, collect() runs its update on the batch's keypoints -- person_ids(frame)."""
+        if tracker is not None:
+            check(self.L.opk_pose_attach_tracker(self.h, tracker.h))
+            self._tracker = tracker
         for ex, kind in ((face, FACE), (hands, HAND)):
             if ex is None:
                 continue
@@ -953,6 +1113,23 @@ class PoseExtractor:
     def detach(self, kind):
         check(self.L.opk_pose_detach_extractor(self.h, kind))
         self._attached.pop(kind, None)
+
+    def detach_tracker(self):
+        check(self.L.opk_pose_detach_tracker(self.h))
+        self._tracker = None
+
+    def person_ids(self, frame):
+        """int64 [people] ids of a collected frame, person order of keypoints() (needs a tracker)."""
+        ids = np.full(max(self.num_people(frame), 0), -2, np.int64)
+        check(self.L.opk_pose_person_ids(self.h, frame, ids.ctypes.data_as(ctypes.c_void_p)))
+        return ids
+
+    def read_track_times(self):
+        """{batches, pyramid_ms, lk_ms, host_ms} of the attached tracker since the last read."""
+        b, p, l, h = ctypes.c_int(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+        check(self.L.opk_pose_read_track_times(self.h, ctypes.byref(b), ctypes.byref(p),
+                                               ctypes.byref(l), ctypes.byref(h)))
+        return {"batches": b.value, "pyramid_ms": p.value, "lk_ms": l.value, "host_ms": h.value}
 
     def _part_rectangles(self, kind, frame):
         n = max(self.num_people(frame), 0)
@@ -987,10 +1164,12 @@ class PoseExtractor:
 
     def datum(self, frame):
         """datum_keypoint_vector of a collected frame: pose and, for the attached extractors, face
-        and both hands -- ready for people_json / save_people_json."""
+        and both hands -- ready for people_json / save_people_json.  With a tracker attached
+        "person_id" holds its ids, else -1 each."""
         face = self.face_keypoints(frame) if FACE in self._attached else None
         hands = tuple(self.hand_keypoints(frame)) if HAND in self._attached else (None, None)
-        return datum_keypoint_vector(self.keypoints(frame)[0], face, hands)
+        ids = self.person_ids(frame) if self._tracker is not None else None
+        return datum_keypoint_vector(self.keypoints(frame)[0], face, hands, ids)
 
     def read_part_times(self, kind):
         """{batches, crops, host_ms, wait_ms} of the stage since the last read: host time for

@@ -10,6 +10,7 @@
 #include "json.h"
 #include "maps.h"
 #include "output.h"
+#include "track.h"
 
 namespace opk {
 
@@ -364,6 +365,18 @@ int opk_assemble_people_semantics(float* kp_out, float* ks_out, int max_people, 
         const int w = std::min(n, max_people);
         if (w > 0 && kp_out) std::memcpy(kp_out, kp.data(), sizeof(float) * (size_t)w * m.parts * 3);
         if (w > 0 && ks_out) std::memcpy(ks_out, ks.data(), sizeof(float) * w);
+    });
+}
+
+int opk_match_people(const float* entries_host, const long long* entry_ids_host, int n_entries,
+                     const float* people_host, int people, int parts, float inlier_ratio,
+                     float distance, int width, int height, long long* next_id, long long* ids_host)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t), "ids are 64-bit");
+    return guarded([&] {
+        opk::match_people(entries_host, reinterpret_cast<const int64_t*>(entry_ids_host), n_entries,
+                          people_host, people, parts, inlier_ratio, distance, width, height,
+                          reinterpret_cast<int64_t*>(next_id), reinterpret_cast<int64_t*>(ids_host));
     });
 }
 

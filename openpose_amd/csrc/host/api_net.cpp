@@ -10,6 +10,7 @@
 #include "extract.h"
 #include "input.h"
 #include "pose.h"
+#include "track.h"
 
 namespace opk {
 template <class F>
@@ -1006,6 +1007,171 @@ int opk_pose_render_frames_parts(opk_pose* p, uint8_t* dst, size_t dst_step, int
     return opk_pose_render_frames_parts_fmt(p, dst, dst_step, out_w, out_h, &f, scale, threshold,
                                             alpha, googly_eyes, blend_original, cast,
                                             face_threshold, face_alpha, hand_threshold, hand_alpha);
+}
+
+}  // extern "C"
+
+// ---- person ids across frames (host/track.h, kernels/track.hip) ---------------------------------
+struct opk_tracker {
+    opk_ctx* ctx;
+    std::unique_ptr<opk::Tracker> t;
+};
+
+extern "C" {
+
+int opk_pyramid_layout(int width, int height, int levels, int* level_w, int* level_h,
+                       size_t* level_offset, size_t* frame_bytes)
+{
+    return guarded_net([&] {
+        const opk::PyramidLayout L = opk::pyramid_layout(width, height, levels);
+        for (int l = 0; l < levels; ++l) {
+            if (level_w) level_w[l] = L.w[l];
+            if (level_h) level_h[l] = L.h[l];
+            if (level_offset) level_offset[l] = L.at[l];
+        }
+        if (frame_bytes) *frame_bytes = L.frame;
+    });
+}
+
+int opk_pyramid_build(opk_ctx* ctx, void* pyramid_dev, const opk_frames* frames, int levels)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(ctx, "NULL ctx");
+        OPK_CHECK_ARG(frames, "NULL frames");
+        const opk::FrameSource src = opk::frame_source(*frames);
+        OPK_CHECK_ARG(src.w > 0 && src.h > 0, "empty frame");
+        const opk::PyramidLayout L = opk::pyramid_layout(src.w, src.h, levels);
+        if (src.n == 0) return;
+        ctx->bind();
+        opk::launch_pyramid(static_cast<uint8_t*>(pyramid_dev), L, src, ctx->stream);
+    });
+}
+
+int opk_pyramid_level(opk_ctx* ctx, float* dst_dev, const void* pyramid_dev, int n, int width,
+                      int height, int levels, int level)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(ctx, "NULL ctx");
+        const opk::PyramidLayout L = opk::pyramid_layout(width, height, levels);
+        OPK_CHECK_ARG(n >= 0, "negative frame count");
+        OPK_CHECK_ARG(level >= 0 && level < levels, "no such pyramid level");
+        if (n == 0) return;
+        ctx->bind();
+        opk::launch_pyramid_level(dst_dev, static_cast<const uint8_t*>(pyramid_dev), L, n, level,
+                                  ctx->stream);
+    });
+}
+
+int opk_lk_points(opk_ctx* ctx, const void* pyramid_dev, int n_frames, const void* carry_dev,
+                  int width, int height, opk_lk_point* points_dev, int npoints)
+{
+    static_assert(sizeof(opk_lk_point) == sizeof(opk::LkPoint), "opk_lk_point is kernels.h's LkPoint");
+    return guarded_net([&] {
+        OPK_CHECK_ARG(ctx, "NULL ctx");
+        const opk::PyramidLayout L = opk::pyramid_layout(width, height, opk::kPyramidLevels);
+        OPK_CHECK_ARG(npoints >= 0 && n_frames >= 0, "negative count");
+        if (npoints == 0) return;
+        ctx->bind();
+        opk::launch_lk_points(reinterpret_cast<opk::LkPoint*>(points_dev), npoints,
+                              static_cast<const uint8_t*>(pyramid_dev), n_frames,
+                              static_cast<const uint8_t*>(carry_dev), L, ctx->stream);
+    });
+}
+
+int opk_tracker_create(opk_ctx* ctx, float confidence, float inlier_ratio, float distance,
+                       int frames_to_delete, opk_tracker** out)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(ctx && out, "NULL argument");
+        *out = new opk_tracker{ctx, std::make_unique<opk::Tracker>(ctx, confidence, inlier_ratio,
+                                                                   distance, frames_to_delete)};
+    });
+}
+
+int opk_tracker_destroy(opk_tracker* t)
+{
+    return guarded_net([&] {
+        if (!t) return;
+        if (t->ctx->device >= 0) t->ctx->bind();
+        delete t;
+    });
+}
+
+int opk_tracker_reset(opk_tracker* t)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(t, "NULL tracker");
+        t->t->reset();
+    });
+}
+
+int opk_tracker_update(opk_tracker* t, const opk_frames* frames, const float* keypoints_host,
+                       const int* people_per_frame, int parts, long long* ids_host)
+{
+    static_assert(sizeof(long long) == sizeof(int64_t), "ids are 64-bit");
+    return guarded_net([&] {
+        OPK_CHECK_ARG(t, "NULL tracker");
+        OPK_CHECK_ARG(frames, "NULL frames");
+        const opk::FrameSource src = opk::frame_source(*frames);
+        OPK_CHECK_ARG(parts > 0, "no parts");
+        if (src.n == 0) return;
+        t->t->build(0, src, t->ctx->stream);
+        t->t->update(0, keypoints_host, people_per_frame, src.n, parts,
+                     reinterpret_cast<int64_t*>(ids_host));
+    });
+}
+
+int opk_tracker_set_timing(opk_tracker* t, int enable)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(t, "NULL tracker");
+        t->t->set_timing(enable != 0);
+    });
+}
+
+int opk_tracker_read_times(opk_tracker* t, int* batches, double* pyramid_ms, double* lk_ms,
+                           double* host_ms, size_t* device_bytes)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(t, "NULL tracker");
+        t->t->read_times(batches, pyramid_ms, lk_ms, host_ms);
+        if (device_bytes) *device_bytes = t->t->device_bytes();
+    });
+}
+
+int opk_pose_attach_tracker(opk_pose* p, opk_tracker* t)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p && t, "NULL argument");
+        p->pose->attach_tracker(t->t.get());
+    });
+}
+
+int opk_pose_detach_tracker(opk_pose* p)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        p->pose->detach_tracker();
+    });
+}
+
+int opk_pose_person_ids(opk_pose* p, int frame, long long* ids_host)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        const std::vector<int64_t>& ids = p->pose->person_ids(frame);
+        OPK_CHECK_ARG(ids.empty() || ids_host, "NULL ids");
+        if (!ids.empty()) std::memcpy(ids_host, ids.data(), ids.size() * sizeof(int64_t));
+    });
+}
+
+int opk_pose_read_track_times(opk_pose* p, int* batches, double* pyramid_ms, double* lk_ms,
+                              double* host_ms)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        p->pose->read_track_times(batches, pyramid_ms, lk_ms, host_ms);
+    });
 }
 
 }  // extern "C"

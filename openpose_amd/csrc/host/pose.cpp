@@ -267,6 +267,66 @@ void PoseHip::need_frames() const
     if (any_attached() && !cur_raw_.plane[0])
         throw Error(3, "face / hand extraction needs the frames: with an extractor attached only "
                        "submit_frames / forward_frames are accepted");
+    if (tracker_attached() && !cur_raw_.plane[0])
+        throw Error(3, "person ids need the frames: with a tracker attached only submit_frames / "
+                       "forward_frames are accepted");
+}
+
+void PoseHip::attach_tracker(Tracker* t)
+{
+    OPK_CHECK_ARG(t != nullptr, "NULL tracker");
+    OPK_CHECK_ARG(t->context() == ctx_, "the tracker and the pose extractor must share one context");
+    if (count_ != 0) throw Error(3, "batches in flight: collect them before attaching");
+    if (tracker_attached()) throw Error(3, "a tracker is already attached: detach it first");
+    tracker_ = t;
+    tracker_alive_ = t->liveness();
+    ids_valid_ = false;
+}
+
+void PoseHip::detach_tracker()
+{
+    if (count_ != 0) throw Error(3, "batches in flight: collect them before detaching");
+    tracker_ = nullptr;
+    tracker_alive_.reset();
+    ids_valid_ = false;
+}
+
+const std::vector<int64_t>& PoseHip::person_ids(int f) const
+{
+    if (!tracker_attached()) throw Error(3, "no tracker attached");
+    if (!ids_valid_) throw Error(3, "no collected batch with person ids");
+    OPK_CHECK_ARG(f >= 0 && f < n_, "bad frame");
+    return ids_[f];
+}
+
+void PoseHip::read_track_times(int* batches, double* pyramid_ms, double* lk_ms, double* host_ms)
+{
+    if (!tracker_attached()) throw Error(3, "no tracker attached");
+    tracker_->read_times(batches, pyramid_ms, lk_ms, host_ms);
+}
+
+void PoseHip::run_tracker(const Slot& sl, int slot)
+{
+    ids_valid_ = false;
+    if (!tracker_attached()) return;
+    if (!sl.raw.plane[0]) throw Error(3, "person ids need the frames of the collected batch");
+    const int n = sl.n;
+    const int parts = pose_model(model_).parts;
+    std::vector<float> kp;
+    size_t total = 0;
+    for (int f = 0; f < n; ++f) {
+        kp.insert(kp.end(), kp_[f].begin(), kp_[f].begin() + (size_t)people_[f] * parts * 3);
+        total += (size_t)people_[f];
+    }
+    std::vector<int64_t> flat(total);
+    tracker_->update(slot, kp.data(), people_.data(), n, parts, flat.data());
+    ids_.assign(n, {});
+    size_t at = 0;
+    for (int f = 0; f < n; ++f) {
+        ids_[f].assign(flat.begin() + (long)at, flat.begin() + (long)(at + people_[f]));
+        at += (size_t)people_[f];
+    }
+    ids_valid_ = true;
 }
 
 void PoseHip::attach_extractor(KeypointExtractor* ex)
@@ -451,6 +511,8 @@ void PoseHip::submit_frames(const FrameSource& frames)
     have_ratios_ = true;
     cur_raw_ = frames;   // a copy, kept in the batch's slot (submit_outputs)
     try {
+        // the batch's pyramid, into the slot submit_outputs is about to fill, ahead of its nets
+        if (tracker_attached()) tracker_->build((head_ + count_) & 1, frames, ctx_->stream);
         if (scale_number_ == 1)
             submit(ptrs[0], n, hw[0], hw[1], w, h);
         else
@@ -787,6 +849,7 @@ int PoseHip::collect()
     scale_net_to_output_ = sl.scale;
     heat_valid_ = false;
     run_parts(sl);   // the attached face / hand extractors, on this batch's frames
+    run_tracker(sl, si);   // the attached tracker: LK and matching of this batch's frames
     return n;
 }
 

@@ -8,6 +8,7 @@
 #include "extract.h"
 #include "net.h"
 #include "pool.h"
+#include "track.h"
 
 namespace opk {
 
@@ -122,6 +123,17 @@ public:
     // since the last read: batches and crops run, host ms for rectangles, crop validity and
     // tables, ms waiting for the device
     void read_part_times(int kind, int* batches, int* crops, double* host_ms, double* wait_ms);
+    // Person ids (the reference's --identification: PoseExtractor::extractIds behind the pose
+    // worker): one Tracker of this context, under the rules of the face / hand stages -- raw-frame
+    // path only, no attach / detach with batches in flight, the submitted frames stay unchanged
+    // until collected.  submit_frames queues the batch's pyramid on the context stream; collect()
+    // runs Tracker::update on the batch's keypoints after run_parts, on the context stream.
+    void attach_tracker(Tracker* t);
+    void detach_tracker();
+    bool tracker_attached() const { return tracker_ != nullptr && !tracker_alive_.expired(); }
+    // ids of frame f of the last collected batch (an OPK_ERR_STATE error without tracker or batch)
+    const std::vector<int64_t>& person_ids(int f) const;
+    void read_track_times(int* batches, double* pyramid_ms, double* lk_ms, double* host_ms);
     // device scratch of the face / hand layers of a batch render (grows, never shrinks)
     void* part_render_scratch(int kind, size_t bytes) { return part_dev_[kind & 1].get(bytes); }
 
@@ -160,6 +172,11 @@ private:
     bool any_attached() const { return attached(0) || attached(1); }
     void need_frames() const;         // the OPK_ERR_STATE of a submit without frames
     void run_parts(const Slot& sl);
+    Tracker* tracker_ = nullptr;
+    std::weak_ptr<void> tracker_alive_;   // Tracker::liveness
+    std::vector<std::vector<int64_t>> ids_;   // the collected batch's, per frame
+    bool ids_valid_ = false;
+    void run_tracker(const Slot& sl, int slot);
     struct NetOutput {
         const float* ptr;
         int h, w;

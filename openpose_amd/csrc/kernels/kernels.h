@@ -130,6 +130,34 @@ void launch_cvmat_to_input_yuv(float* dst, const FrameSource& src, int n, int dh
                                int normalize, hipStream_t stream, const int* frame_of,
                                int tab_stride);
 
+// ---- person ids across frames (track.hip; the definition: include/opk.h) ------------------------
+// The pyramid of one frame is one record of `frame` bytes: level 0 (the grey image) as uint8
+// [h][w] at at[0], level 1 as uint16 (256 x value) at at[1], level 2 as float at at[2]; every level
+// starts on a 16-byte boundary of the record.  A batch is n records one after the other.
+constexpr int kPyramidLevels = 3;
+struct PyramidLayout {
+    int levels;
+    int w[kPyramidLevels], h[kPyramidLevels];
+    size_t at[kPyramidLevels];
+    size_t frame;
+};
+PyramidLayout pyramid_layout(int width, int height, int levels);   // OPK_ERR_ARG: levels not 1..3
+// grey + levels 1 .. L.levels - 1 of the frames `src` (BGR, NV12, I420) into pyr [src.n records]
+void launch_pyramid(uint8_t* pyr, const PyramidLayout& L, const FrameSource& src, hipStream_t stream);
+// dst [n][h][w] fp32 = level `level` of n records
+void launch_pyramid_level(float* dst, const uint8_t* pyr, const PyramidLayout& L, int n, int level,
+                          hipStream_t stream);
+// opk_lk_point: frames frame_i -> frame_j index the records of pyr, -1 the one record `carry`
+struct LkPoint {
+    int frame_i, frame_j;
+    float x, y;
+    int status;
+};
+// every record with status 0 is propagated in place; a frame index outside the buffers (-1 with a
+// NULL carry included) gives status 3 and is never followed
+void launch_lk_points(LkPoint* points, int npoints, const uint8_t* pyr, int nframes,
+                      const uint8_t* carry, const PyramidLayout& L, hipStream_t stream);
+
 // ---- crops of face / hand keypoint extraction (crop.hip) -----------------------------------------
 // peaks [crops][parts][3] = (x, y, value) of the maximum of each of the first `parts` channels of
 // `heat` (frames = crops), the first in raster order among equal values (cv::minMaxLoc)
