@@ -336,8 +336,8 @@ int opk_bgr_to_frames(opk_ctx* ctx, const opk_frames_out* dst, const opk_frames*
 
 /* Kernel-variant switches (no reference counterpart; A/B tests and tuning only): key = one of
  * "CONV3_SMALL", "CONV3_W16", "CONV3_PERSIST", "CONV3_WIDE", "CONV3P_ASMR", "CONV3P_WIDE",
- * "CONV3P_PRIO", "CONV3W", "CONV1_TILE", "CONV1_N64W16", "CONV1_FUSED", "CONV3S_MAX", "LK_WAVE" (read
- * when a launch is planned);
+ * "CONV3P_PRIO", "CONV3W", "CONV1_TILE", "CONV1_N64W16", "CONV1_FUSED", "CONV3S_MAX", "LK_WAVE",
+ * "TRI_GROUP" (read when a launch is planned);
  * reset != 0 removes the key (back to the product default).  Process-wide; the environment is
  * never consulted. */
 int opk_dev_set(const char* key, int value, int reset);
@@ -870,6 +870,111 @@ int opk_pose_person_ids(opk_pose* pose, int frame, long long* ids_host);
 /* opk_tracker_read_times of the attached tracker */
 int opk_pose_read_track_times(opk_pose* pose, int* batches, double* pyramid_ms, double* lk_ms,
                               double* host_ms);
+
+/* ---- 3-D keypoints from a camera rig: op::PoseTriangulation::reconstructArray behind
+ * op::WPoseTriangulation (--3d; include/openpose/3d/wPoseTriangulation.hpp:62-100,
+ * src/openpose/3d/poseTriangulation.cpp:8-166, src/openpose/3d/poseTriangulationPrivate.cpp:11-33,
+ * 119-226), the reference's default build: the USE_CERES refinement (poseTriangulationPrivate.cpp:
+ * 228-290) is out of scope, as are the calibration files, --frame_undistort and the 3-D renderer.
+ * The reference takes the null vector of each point's matrix from OpenCV's cv::SVD; OpenCV is not
+ * here, so this text is the definition -- a one-sided Jacobi of the form cv::SVD's JacobiSVDImpl_
+ * has -- and parity with cv::SVD is by restatement only (tests/triangulate_cases.py, which is also
+ * held against LAPACK's SVD: every float within 1 ulp, every decision equal).
+ * Everything is fp64 unless named, with every multiply and add rounded separately and correctly
+ * rounded division and square root.  A NaN is any NaN: payload and sign are not defined.
+ *
+ * RIG (opk_rig).  V views, 2 <= V <= 7 (the reference refuses a point seen by 8 or more,
+ *   poseTriangulationPrivate.cpp:163-170); per view a 3x4 row-major double camera matrix P and an
+ *   image size (w, h) with w, h > 0 and w*h an int.  V outside 2..7, a matrix entry that is not
+ *   finite or a bad size is OPK_ERR_ARG.  min_views is >= 2 or negative; 0 and 1 are OPK_ERR_ARG
+ *   (the PoseTriangulation constructor, poseTriangulation.cpp:168-182); negative means
+ *   max(2, min(4, V-1)).
+ *
+ * INPUT.  Per time step and view one array [parts][3] of (x, y, score) in float -- person 0 of
+ *   that view, as the reference indexes it -- and a `present` flag: whether the view has any person
+ *   (its array is not empty).
+ *
+ * STEP RESULT.  Fewer than 2 present views: the empty array, status 0 (the reference's "not a 3-D
+ *   problem").  Otherwise a part is valid in a view when the view is present and score > 0.35f &&
+ *   x > 8 && x < w-8 && y > 8 && y < h-8 (isValidKeypoint): strict, in float against the int
+ *   bounds converted to float, so NaN and infinities never get in.  A part is attempted when its
+ *   valid views number >= the effective min_views.  No attempted part: status 0.  Otherwise status 1
+ *   and the result is [parts][4], zeros but for the parts written below.
+ *
+ * ONE TRIANGULATION over a set S of views.  A is 2V x 4: rows 2i and 2i+1 are x_i*P_i[2] - P_i[0]
+ *   and y_i*P_i[2] - P_i[1] for i in S (x_i, y_i the floats as doubles) and zero for a view outside
+ *   S -- the shape is fixed and every sum gains exact zeros.  The null vector by cyclic one-sided
+ *   Jacobi on the four columns: W[i] = the squared norm of column i, summed over the rows in order
+ *   from 0; V = I; up to 30 sweeps over the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3).  For a pair
+ *   (i, j): p = the sum over the rows k, in order from 0, of A[k][i]*A[k][j]; the pair is skipped
+ *   when |p| <= DBL_EPSILON*sqrt(W[i]*W[j]); otherwise p *= 2, beta = W[i]-W[j], gamma =
+ *   sqrt(p*p + beta*beta) and
+ *     beta < 0:  delta = (gamma-beta)*0.5,  s = sqrt(delta/gamma),  c = p/(gamma*s*2);
+ *     else:      c = sqrt((gamma+beta)/(gamma*2)),  s = p/(gamma*c*2)
+ *   (products left to right); every row of both columns is rotated, t0 = c*a_i + s*a_j, t1 =
+ *   c*a_j - s*a_i, W[i] and W[j] are summed again from the rotated entries, and the four rows of V
+ *   get the same rotation.  A sweep without a rotation ends the loop.  The null vector v is the
+ *   column of V with the smallest W, the lowest index among equals (found by `W[i] < smallest`).
+ *   X = v / v[3], all four components divided.  The reprojection error is the sum over i in S, in
+ *   view order from 0, of sqrt(dx*dx + dy*dy), divided by the size of S, where (u, v, w) = P_i X,
+ *   each row the sum over k = 0..3 in order from 0, dx = u/w - x_i, dy = v/w - y_i.
+ *
+ * ONE POINT.  Triangulate over its valid views: error e.  When the valid views number >= 4 and
+ *   e > 0.5*maxAcc, leave one out: best = e; for each valid view i in view order, triangulate
+ *   without it, error e_i; if best > e_i && e_i < 0.9*e the subset becomes the best.  If one did,
+ *   the point, its error and its dropped view (the rig's index of i) are that subset's.
+ *   maxAcc = 25*sqrt(w0*h0/1310720.), w0*h0 the int product of view 0's size.
+ *
+ * ONE ARRAY OF A STEP.  total = the sum of the attempted parts' errors in part order from 0,
+ *   divided by their count.  A part is written as (float)x, (float)y, (float)z, 1 when the three
+ *   floats are finite && err < 5*total && err < maxAcc.  It follows that one NaN error makes total
+ *   NaN and so rejects every part of that array (the status stays 1: the array is all zeros) --
+ *   two identical cameras at the origin do that.
+ *
+ * opk_camera_matrix: out[3][4] = intrinsics[3][3] * extrinsics[3][4], the product
+ *   cameraParameterReader.cpp:72 forms; each entry the sum over k = 0..2 in order from 0.
+ * opk_triangulate_host: a pure host function (no context).  keypoints_host [steps][V][parts][3],
+ *   present_host [steps][V] (0 / not 0); xyz_host [steps][parts][4] (zeros for status 0),
+ *   status_host [steps]; optional errors_host [steps][parts] (-1 where the part was not
+ *   attempted) and dropped_host [steps][parts] (the dropped view, or -1).
+ * opk_triangulate: the same call on device buffers, enqueued on the context's stream: one launch
+ *   over the points (8 lanes per point: lane 0 over all valid views, lane s without view s-1, the
+ *   choice a shuffle minimum with the lowest view winning ties -- the sequential rule's choice)
+ *   and one small launch for each array's total and acceptance, a sequential walk.  The rig is
+ *   read on the host before the call returns.  Bit for bit opk_triangulate_host.
+ * Both replace PoseTriangulation::reconstructArray for one kind of array; INTEGRATION.md. */
+typedef struct opk_rig {
+    int views;                      /* V */
+    const double* camera_matrices;  /* [V][3][4] */
+    const int* image_sizes;         /* [V][2]: width, height */
+    int min_views;                  /* --3d_min_views: >= 2, or negative */
+} opk_rig;
+int opk_camera_matrix(const double* intrinsics, const double* extrinsics, double* out);
+int opk_triangulate_host(const opk_rig* rig, int steps, int parts, const float* keypoints_host,
+                         const int* present_host, float* xyz_host, int* status_host,
+                         double* errors_host, int* dropped_host);
+int opk_triangulate(opk_ctx* ctx, const opk_rig* rig, int steps, int parts,
+                    const float* keypoints_dev, const int* present_dev, float* xyz_dev,
+                    int* status_dev, double* errors_dev, int* dropped_dev);
+/* The rig as a stage of the pose pipeline (WPoseTriangulation), under the attach rules of
+ * opk_pose_attach_tracker: setting or clearing (rig NULL) with batches in flight is OPK_ERR_STATE;
+ * the rig is copied.  While set, a batch of n frames is n / V time steps, frame t*V + v the view v
+ * of step t: n not a multiple of V, or a frame size other than the rig's for that view, is
+ * OPK_ERR_ARG at submit.  opk_pose_collect then, after the people assembly and the face / hand
+ * stages, uploads person 0 of every frame (present: the frame has a person) for the body array
+ * and, where extractors are attached, the face and both hand arrays, runs opk_triangulate once per
+ * array kind on the context stream -- behind the nets of the next batch that an earlier submit
+ * queued -- and downloads the results.
+ * opk_pose_keypoints_3d: xyz_host [parts][4] of the kind (the model's parts, 70, 21, 21) and the
+ * status of one step of the collected batch; every frame of the step carries these arrays
+ * (wPoseTriangulation.hpp:94-100).  OPK_ERR_STATE without views, without a batch collected with
+ * them, or for a face / hand kind whose extractor is not attached. */
+#define OPK_3D_BODY 0
+#define OPK_3D_FACE 1
+#define OPK_3D_HAND_LEFT 2
+#define OPK_3D_HAND_RIGHT 3
+int opk_pose_set_views(opk_pose* pose, const opk_rig* rig);
+int opk_pose_keypoints_3d(opk_pose* pose, int step, int kind, float* xyz_host, int* status);
 
 /* ---- Measured ceilings (no reference counterpart; SURVEY.md §8d "confirm the vendor peaks"):
  *      dense fp16 MFMA rate of v_mfma_f32_16x16x32_f16 from registers (the conv kernels'

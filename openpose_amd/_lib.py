@@ -188,6 +188,12 @@ _SIGS = {
     "opk_pose_detach_tracker": (_i, [_p]),
     "opk_pose_person_ids": (_i, [_p, _i, _p]),
     "opk_pose_read_track_times": (_i, [_p, _ip, _c.POINTER(_d), _c.POINTER(_d), _c.POINTER(_d)]),
+    # 3-D keypoints from a camera rig (RigStruct)
+    "opk_camera_matrix": (_i, [_p, _p, _p]),
+    "opk_triangulate_host": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "opk_triangulate": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "opk_pose_set_views": (_i, [_p, _p]),
+    "opk_pose_keypoints_3d": (_i, [_p, _i, _i, _p, _ip]),
 }
 
 
@@ -195,6 +201,11 @@ class FramesStruct(ctypes.Structure):
     """opk_frames (include/opk.h)."""
     _fields_ = [("format", _i), ("n", _i), ("width", _i), ("height", _i), ("plane", _p * 3),
                 ("step", _c.c_size_t * 3), ("frame_bytes", _c.c_size_t * 3)]
+
+
+class RigStruct(ctypes.Structure):
+    """opk_rig (include/opk.h)."""
+    _fields_ = [("views", _i), ("camera_matrices", _p), ("image_sizes", _p), ("min_views", _i)]
 
 
 class FramesOutStruct(ctypes.Structure):

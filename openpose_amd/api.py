@@ -691,20 +691,22 @@ def save_people_json(path, keypoint_vector, candidates=None, human_readable=Fals
 
 
 def datum_keypoint_vector(pose_keypoints, face_keypoints=None, hand_keypoints=(None, None),
-                          person_ids=None):
+                          person_ids=None, pose_keypoints_3d=None, face_keypoints_3d=None,
+                          hand_keypoints_3d=(None, None)):
     """The keypointVector WPeopleJsonSaver builds from a Datum (wPeopleJsonSaver.hpp:75-88):
     person ids (-1 each without a person-id extractor, PoseExtractor::extractIds,
     poseExtractor.cpp:136-151; person_ids: a Tracker's), the 2-D body / face / hand arrays and the
-    (empty) 3-D ones."""
+    3-D ones ([1, parts, 4] of a rig's time step, PoseExtractor.keypoints_3d; empty without)."""
     pk = np.asarray(pose_keypoints, np.float32)
     ids = np.full(pk.shape[0], -1, np.float32) if pk.size else None
     if person_ids is not None and pk.size:
         ids = np.asarray(person_ids, np.float32)
     return [(ids, "person_id"), (pk, "pose_keypoints_2d"), (face_keypoints, "face_keypoints_2d"),
             (hand_keypoints[0], "hand_left_keypoints_2d"),
-            (hand_keypoints[1], "hand_right_keypoints_2d"), (None, "pose_keypoints_3d"),
-            (None, "face_keypoints_3d"), (None, "hand_left_keypoints_3d"),
-            (None, "hand_right_keypoints_3d")]
+            (hand_keypoints[1], "hand_right_keypoints_2d"),
+            (pose_keypoints_3d, "pose_keypoints_3d"), (face_keypoints_3d, "face_keypoints_3d"),
+            (hand_keypoints_3d[0], "hand_left_keypoints_3d"),
+            (hand_keypoints_3d[1], "hand_right_keypoints_3d")]
 
 
 def caffemodel_blob(path, layer, index):
@@ -885,6 +887,89 @@ class Tracker:
                                             ctypes.byref(h), ctypes.byref(m)))
         return {"batches": b.value, "pyramid_ms": p.value, "lk_ms": l.value, "host_ms": h.value,
                 "device_bytes": m.value}
+
+
+def camera_matrix(K, Rt):
+    """opk_camera_matrix: the 3x4 camera matrix K [3, 3] x Rt [3, 4] (cameraParameterReader.cpp:72),
+    every entry a sequential fp64 sum."""
+    K = np.ascontiguousarray(K, np.float64)
+    Rt = np.ascontiguousarray(Rt, np.float64)
+    assert K.shape == (3, 3) and Rt.shape == (3, 4)
+    out = np.zeros((3, 4), np.float64)
+    check(_lib.load().opk_camera_matrix(K.ctypes.data_as(ctypes.c_void_p),
+                                        Rt.ctypes.data_as(ctypes.c_void_p),
+                                        out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+KIND_3D_BODY, KIND_3D_FACE, KIND_3D_HAND_LEFT, KIND_3D_HAND_RIGHT = 0, 1, 2, 3   # OPK_3D_*
+
+
+class Triangulator:
+    """3-D keypoints from a camera rig (op::PoseTriangulation, --3d; include/opk.h): V = 2..7 views,
+    camera_matrices [V, 3, 4] float64, image_sizes [V, 2] (width, height), min_views >= 2 or
+    negative (max(2, min(4, V-1)))."""
+
+    def __init__(self, camera_matrices, image_sizes, min_views=-1):
+        self.P = np.ascontiguousarray(camera_matrices, np.float64)
+        self.sizes = np.ascontiguousarray(image_sizes, np.int32)
+        if self.P.ndim != 3 or self.P.shape[1:] != (3, 4) or self.sizes.shape != (self.P.shape[0], 2):
+            raise ValueError("camera_matrices [V, 3, 4] and image_sizes [V, 2]")
+        self.views = self.P.shape[0]
+        self.min_views = int(min_views)
+        # the library's checks (OPK_ERR_ARG: V outside 2..7, min_views 0 / 1, a non-finite entry)
+        one = np.zeros((1, self.views, 1, 3), np.float32)
+        self._host(one, np.ones((1, self.views), np.int32))
+
+    def struct(self):
+        return _lib.RigStruct(self.views, self.P.ctypes.data, self.sizes.ctypes.data, self.min_views)
+
+    def _host(self, kp, present):
+        steps, _, parts, _ = kp.shape
+        xyz = np.zeros((steps, parts, 4), np.float32)
+        status = np.zeros(steps, np.int32)
+        errors = np.zeros((steps, parts), np.float64)
+        dropped = np.zeros((steps, parts), np.int32)
+        rig = self.struct()
+        v = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        check(_lib.load().opk_triangulate_host(ctypes.byref(rig), steps, parts, v(kp), v(present),
+                                               v(xyz), v(status), v(errors), v(dropped)))
+        return xyz, status, errors, dropped
+
+    def reconstruct(self, keypoints, present=None, device=None):
+        """keypoints [steps, V, parts, 3] (x, y, score; person 0 of each view), present [steps, V]
+        (default: every view has a person).  device None: opk_triangulate_host; a Context:
+        opk_triangulate on its stream (numpy or CUDA inputs), bit for bit the same.  Returns (xyz
+        float32 [steps, parts, 4], status int32 [steps], errors float64 [steps, parts] with -1 where
+        a part was not attempted, dropped int32 [steps, parts] with -1 for none)."""
+        on_dev = torch.is_tensor(keypoints)
+        kshape = tuple(keypoints.shape)
+        if len(kshape) != 4 or kshape[1] != self.views or kshape[3] != 3 or kshape[2] < 1:
+            raise ValueError("keypoints [steps, %d, parts, 3]" % self.views)
+        steps, _, parts, _ = kshape
+        if present is None:
+            present = np.ones((steps, self.views), np.int32)
+        if device is None:
+            kp = np.ascontiguousarray(keypoints.cpu().numpy() if on_dev else keypoints, np.float32)
+            pr = np.ascontiguousarray(present.cpu().numpy() if torch.is_tensor(present) else present,
+                                      np.int32).reshape(steps, self.views)
+            return self._host(kp, pr)
+        ctx = device
+        kp = keypoints if on_dev else torch.from_numpy(np.ascontiguousarray(keypoints, np.float32))
+        kp = kp.to("cuda", torch.float32).contiguous()
+        pr = present if torch.is_tensor(present) else torch.from_numpy(
+            np.ascontiguousarray(present, np.int32))
+        pr = pr.to("cuda", torch.int32).reshape(steps, self.views).contiguous()
+        xyz = torch.empty((steps, parts, 4), dtype=torch.float32, device="cuda")
+        status = torch.empty(steps, dtype=torch.int32, device="cuda")
+        errors = torch.empty((steps, parts), dtype=torch.float64, device="cuda")
+        dropped = torch.empty((steps, parts), dtype=torch.int32, device="cuda")
+        rig = self.struct()
+        check(ctx.L.opk_triangulate(ctx.h, ctypes.byref(rig), steps, parts, _ptr(kp), _ptr(pr),
+                                    _ptr(xyz), _ptr(status), _ptr(errors), _ptr(dropped)))
+        ctx.sync()
+        return (xyz.cpu().numpy(), status.cpu().numpy(), errors.cpu().numpy(),
+                dropped.cpu().numpy())
 
 
 class Net:
@@ -1083,6 +1168,7 @@ class PoseExtractor:
         self.pose_model = pose_model
         self._attached = {}   # kind -> KeypointExtractor (kept alive while attached)
         self._tracker = None  # the attached Tracker
+        self._views = None    # the Triangulator of set_views
 
     def close(self):
         if self.h:
@@ -1090,6 +1176,7 @@ class PoseExtractor:
             self.h = None
             self._attached = {}
             self._tracker = None
+            self._views = None
 
     # ---- face / hand stages (opk_pose_attach_extractor) ---------------------------------------
     def attach(self, face=None, hands=None, tracker=None):
@@ -1117,6 +1204,41 @@ class PoseExtractor:
     def detach_tracker(self):
         check(self.L.opk_pose_detach_tracker(self.h))
         self._tracker = None
+
+    # ---- 3-D keypoints (opk_pose_set_views) ----------------------------------------------------
+    def set_views(self, tri):
+        """A Triangulator: from now on a batch of n frames is n / V time steps of its rig, frame
+        t*V + v the view v of step t, and collect() reconstructs person 0 of every step --
+        keypoints_3d(step), datum(frame).  None clears.  Not with batches in flight.
+        The mode is the reference's --3d, which demands --number_people_max 1: only person 0 of a
+        frame is reconstructed, and people_json refuses a datum whose 2-D arrays hold more people
+        than its 3-D ones -- cut such a frame to its first person before writing it."""
+        if tri is None:
+            check(self.L.opk_pose_set_views(self.h, None))
+        else:
+            rig = tri.struct()
+            check(self.L.opk_pose_set_views(self.h, ctypes.byref(rig)))
+        self._views = tri
+
+    def keypoints_3d(self, step):
+        """The four 3-D arrays of a collected time step, body, face, left hand, right hand: each
+        float32 [1, parts, 4] (x, y, z, 1 or zeros), or empty where the step's status is 0 or the
+        extractor is not attached."""
+        out = []
+        for kind, on, parts in ((KIND_3D_BODY, True, self.parts),
+                                (KIND_3D_FACE, FACE in self._attached, 70),
+                                (KIND_3D_HAND_LEFT, HAND in self._attached, 21),
+                                (KIND_3D_HAND_RIGHT, HAND in self._attached, 21)):
+            if kind and on:
+                parts = self._attached[FACE if kind == KIND_3D_FACE else HAND].parts
+            xyz = np.zeros((1, parts, 4), np.float32)
+            st = ctypes.c_int(0)
+            if on or not kind:
+                check(self.L.opk_pose_keypoints_3d(self.h, step, kind,
+                                                   xyz.ctypes.data_as(ctypes.c_void_p),
+                                                   ctypes.byref(st)))
+            out.append(xyz if st.value else np.zeros((0, parts, 4), np.float32))
+        return out
 
     def person_ids(self, frame):
         """int64 [people] ids of a collected frame, person order of keypoints() (needs a tracker)."""
@@ -1165,11 +1287,18 @@ class PoseExtractor:
     def datum(self, frame):
         """datum_keypoint_vector of a collected frame: pose and, for the attached extractors, face
         and both hands -- ready for people_json / save_people_json.  With a tracker attached
-        "person_id" holds its ids, else -1 each."""
+        "person_id" holds its ids, else -1 each.  With views set (set_views) the four 3-D arrays of
+        the frame's time step come with it; they hold person 0 only, so for people_json the frame
+        must hold one person (--number_people_max 1) or be cut to its first."""
         face = self.face_keypoints(frame) if FACE in self._attached else None
         hands = tuple(self.hand_keypoints(frame)) if HAND in self._attached else (None, None)
         ids = self.person_ids(frame) if self._tracker is not None else None
-        return datum_keypoint_vector(self.keypoints(frame)[0], face, hands, ids)
+        if self._views is None:
+            return datum_keypoint_vector(self.keypoints(frame)[0], face, hands, ids)
+        # every frame of a time step carries the step's 3-D arrays (wPoseTriangulation.hpp:94-100)
+        body3, face3, left3, right3 = self.keypoints_3d(frame // self._views.views)
+        return datum_keypoint_vector(self.keypoints(frame)[0], face, hands, ids, body3, face3,
+                                     (left3, right3))
 
     def read_part_times(self, kind):
         """{batches, crops, host_ms, wait_ms} of the stage since the last read: host time for

@@ -11,6 +11,7 @@
 #include "maps.h"
 #include "output.h"
 #include "track.h"
+#include "triangulate.h"
 
 namespace opk {
 
@@ -377,6 +378,18 @@ int opk_match_people(const float* entries_host, const long long* entry_ids_host,
         opk::match_people(entries_host, reinterpret_cast<const int64_t*>(entry_ids_host), n_entries,
                           people_host, people, parts, inlier_ratio, distance, width, height,
                           reinterpret_cast<int64_t*>(next_id), reinterpret_cast<int64_t*>(ids_host));
+    });
+}
+
+int opk_triangulate(opk_ctx* ctx, const opk_rig* rig, int steps, int parts,
+                    const float* keypoints_dev, const int* present_dev, float* xyz_dev,
+                    int* status_dev, double* errors_dev, int* dropped_dev)
+{
+    return guarded([&] {
+        OPK_CHECK_ARG(ctx != nullptr, "NULL context");
+        const opk::TriRig r = opk::make_rig(rig);
+        opk::triangulate(ctx, r, steps, parts, keypoints_dev, present_dev, xyz_dev, status_dev,
+                         errors_dev, dropped_dev);
     });
 }
 

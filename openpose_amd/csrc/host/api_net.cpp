@@ -1165,6 +1165,29 @@ int opk_pose_person_ids(opk_pose* p, int frame, long long* ids_host)
     });
 }
 
+int opk_pose_set_views(opk_pose* p, const opk_rig* rig)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        if (!rig) {
+            p->pose->set_views(nullptr);
+            return;
+        }
+        const opk::TriRig r = opk::make_rig(rig);
+        p->pose->set_views(&r);
+    });
+}
+
+int opk_pose_keypoints_3d(opk_pose* p, int step, int kind, float* xyz_host, int* status)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p && xyz_host && status, "NULL argument");
+        int parts = 0;
+        const float* xyz = p->pose->keypoints_3d(step, kind, &parts, status);
+        std::memcpy(xyz_host, xyz, (size_t)parts * 4 * sizeof(float));
+    });
+}
+
 int opk_pose_read_track_times(opk_pose* p, int* batches, double* pyramid_ms, double* lk_ms,
                               double* host_ms)
 {

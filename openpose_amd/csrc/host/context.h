@@ -60,6 +60,7 @@ struct Context {
     DevBuf nms_scratch;
     int* nms_candidates(int frames, int parts);
     HostBuf host_peaks, host_scores;
+    DevBuf tri_errors;       // opk_triangulate without errors_dev: the points' errors
 
     // streams other objects of this context run device work on besides `stream` (PoseHip's
     // post-processing stream, its multi-scale net streams): opk_sync waits for them too

@@ -329,6 +329,106 @@ void PoseHip::run_tracker(const Slot& sl, int slot)
     ids_valid_ = true;
 }
 
+void PoseHip::set_views(const TriRig* rig)
+{
+    if (count_ != 0) throw Error(3, "batches in flight: collect them before setting the views");
+    views_ = rig ? *rig : TriRig{};
+    v3d_valid_ = false;
+}
+
+void PoseHip::check_views(int n, int w, int h) const
+{
+    if (!views_set()) return;
+    OPK_CHECK_ARG(n % views_.views == 0, "with " + std::to_string(views_.views) +
+                                             " views set a batch holds whole time steps: " +
+                                             std::to_string(n) + " frames");
+    for (int v = 0; v < views_.views; ++v)
+        OPK_CHECK_ARG(views_.w[v] == w && views_.h[v] == h,
+                      "frame size differs from the rig's for view " + std::to_string(v));
+}
+
+const float* PoseHip::keypoints_3d(int step, int kind, int* parts, int* status) const
+{
+    OPK_CHECK_ARG(kind >= 0 && kind < 4, "kind: body (0), face (1), left hand (2), right hand (3)");
+    if (!views_set()) throw Error(3, "no views set");
+    if (!v3d_valid_) throw Error(3, "no collected batch with 3-D keypoints");
+    const Array3d& a = v3d_[kind];
+    if (a.parts == 0) throw Error(3, "no such extractor attached");
+    OPK_CHECK_ARG(step >= 0 && step < v3d_steps_, "bad step");
+    *parts = a.parts;
+    *status = a.status[step];
+    return a.xyz.data() + (size_t)step * a.parts * 4;
+}
+
+void PoseHip::run_views(const Slot& sl)
+{
+    v3d_valid_ = false;
+    if (!views_set()) return;
+    const int n = sl.n, V = views_.views, steps = n / V;
+    const int body = pose_model(model_).parts;
+    const bool has[4] = {true, attached(0) && parts_valid_, attached(1) && parts_valid_,
+                         attached(1) && parts_valid_};
+    const int parts[4] = {body, part_[0].parts, part_[1].parts, part_[1].parts};
+    // one staging block: present [n] ints, then per kind its keypoints [n][parts][3], then (results)
+    // per kind xyz [steps][parts][4] and status [steps]
+    size_t kp_at[4], xyz_at[4], st_at[4], at = (size_t)n * sizeof(int);
+    auto pad = [](size_t b) { return (b + 15) / 16 * 16; };
+    at = pad(at);
+    for (int k = 0; k < 4; ++k) {
+        kp_at[k] = at;
+        if (has[k]) at = pad(at + (size_t)n * parts[k] * 3 * sizeof(float));
+    }
+    const size_t in_bytes = at;
+    for (int k = 0; k < 4; ++k) {
+        xyz_at[k] = at;
+        if (has[k]) at = pad(at + (size_t)steps * parts[k] * 4 * sizeof(float));
+        st_at[k] = at;
+        if (has[k]) at = pad(at + (size_t)steps * sizeof(int));
+    }
+    char* host = static_cast<char*>(v3d_host_.get(at));
+    char* dev = static_cast<char*>(v3d_dev_.get(at));
+    std::memset(host, 0, in_bytes);
+    int* present = reinterpret_cast<int*>(host);
+    for (int f = 0; f < n; ++f) {
+        present[f] = people_[f] > 0 ? 1 : 0;
+        if (!present[f]) continue;
+        std::memcpy(host + kp_at[0] + (size_t)f * body * 3 * sizeof(float), kp_[f].data(),
+                    (size_t)body * 3 * sizeof(float));
+        const int first = has[1] || has[2] ? part_first_[f] : 0, total = has[1] || has[2] ? part_first_[n] : 0;
+        if (has[1])
+            std::memcpy(host + kp_at[1] + (size_t)f * parts[1] * 3 * sizeof(float),
+                        part_[0].kp.data() + (size_t)first * parts[1] * 3,
+                        (size_t)parts[1] * 3 * sizeof(float));
+        for (int side = 0; side < 2 && has[2]; ++side)
+            std::memcpy(host + kp_at[2 + side] + (size_t)f * parts[2] * 3 * sizeof(float),
+                        part_[1].kp.data() + ((size_t)side * total + first) * parts[2] * 3,
+                        (size_t)parts[2] * 3 * sizeof(float));
+    }
+    ctx_->bind();
+    OPK_HIP(hipMemcpyAsync(dev, host, in_bytes, hipMemcpyHostToDevice, ctx_->stream));
+    for (int k = 0; k < 4; ++k) {
+        if (!has[k]) continue;
+        triangulate(ctx_, views_, steps, parts[k], reinterpret_cast<const float*>(dev + kp_at[k]),
+                    reinterpret_cast<const int*>(dev), reinterpret_cast<float*>(dev + xyz_at[k]),
+                    reinterpret_cast<int*>(dev + st_at[k]), nullptr, nullptr);
+    }
+    if (at > in_bytes)
+        OPK_HIP(hipMemcpyAsync(host + in_bytes, dev + in_bytes, at - in_bytes, hipMemcpyDeviceToHost,
+                               ctx_->stream));
+    OPK_HIP(hipStreamSynchronize(ctx_->stream));
+    for (int k = 0; k < 4; ++k) {
+        Array3d& a = v3d_[k];
+        a.parts = has[k] ? parts[k] : 0;
+        if (!has[k]) continue;
+        const float* x = reinterpret_cast<const float*>(host + xyz_at[k]);
+        const int* st = reinterpret_cast<const int*>(host + st_at[k]);
+        a.xyz.assign(x, x + (size_t)steps * parts[k] * 4);
+        a.status.assign(st, st + steps);
+    }
+    v3d_steps_ = steps;
+    v3d_valid_ = true;
+}
+
 void PoseHip::attach_extractor(KeypointExtractor* ex)
 {
     OPK_CHECK_ARG(ex != nullptr, "NULL extractor");
@@ -429,6 +529,7 @@ void PoseHip::run_parts(const Slot& sl)
 void PoseHip::submit(const float* frames, int n, int net_h, int net_w, int prod_w, int prod_h)
 {
     need_frames();
+    check_views(n, prod_w, prod_h);
     OPK_CHECK_ARG(net_ != nullptr, "no network: use forward_net_output (poseNetOutput path)");
     OPK_CHECK_ARG(count_ < 2, "two batches already in flight: collect first");
     ctx_->bind();
@@ -490,6 +591,7 @@ void PoseHip::submit_frames(const FrameSource& frames)
     OPK_CHECK_ARG(frames.plane[0] != nullptr && n > 0 && w > 0 && h > 0, "empty frames");
     OPK_CHECK_ARG(count_ < 2, "two batches already in flight: collect first");
     OPK_CHECK_ARG(model_ != 6, "BODY_19N (DenseNet normalisation) is not supported");
+    check_views(n, w, h);
     double scales[kMaxResizeSources];
     scale_and_size(w, h, in_net_w_, in_net_h_, dyn_, scale_number_, scale_gap_, scales, input_hw_);
     const float* ptrs[kMaxResizeSources];
@@ -545,6 +647,7 @@ void PoseHip::submit_multi(const float* const* frames, const int* net_hw, int ns
                            int prod_w, int prod_h)
 {
     need_frames();
+    check_views(n, prod_w, prod_h);
     OPK_CHECK_ARG(net_ != nullptr, "no network: multi-scale needs the net");
     OPK_CHECK_ARG(frames && net_hw && nscales >= 1 && nscales <= kMaxResizeSources,
                   "1..8 scales");
@@ -601,6 +704,7 @@ void PoseHip::submit_net_output(const float* net_out, int n, int oh, int ow, int
                                 int net_w, int prod_w, int prod_h)
 {
     need_frames();
+    check_views(n, prod_w, prod_h);
     const NetOutput o{net_out, oh, ow};
     submit_outputs(&o, 1, n, net_h, net_w, prod_w, prod_h, false);
 }
@@ -849,6 +953,7 @@ int PoseHip::collect()
     scale_net_to_output_ = sl.scale;
     heat_valid_ = false;
     run_parts(sl);   // the attached face / hand extractors, on this batch's frames
+    run_views(sl);   // the rig: 3-D arrays of this batch's time steps
     run_tracker(sl, si);   // the attached tracker: LK and matching of this batch's frames
     return n;
 }

@@ -9,6 +9,7 @@
 #include "net.h"
 #include "pool.h"
 #include "track.h"
+#include "triangulate.h"
 
 namespace opk {
 
@@ -134,6 +135,17 @@ public:
     // ids of frame f of the last collected batch (an OPK_ERR_STATE error without tracker or batch)
     const std::vector<int64_t>& person_ids(int f) const;
     void read_track_times(int* batches, double* pyramid_ms, double* lk_ms, double* host_ms);
+    // 3-D keypoints (the reference's --3d: WPoseTriangulation behind the pose, face and hand
+    // workers): while a rig is set a batch of n frames is n / V time steps, frame t*V + v the view
+    // v of step t (submit checks n and the frame size against the rig); collect(), after
+    // run_parts, uploads person 0 of every frame, runs triangulate() once per array kind (body,
+    // and face / left hand / right hand where attached) on the context stream and downloads the
+    // results.  Set / clear (nullptr) only with no batch in flight.
+    void set_views(const TriRig* rig);
+    bool views_set() const { return views_.views > 0; }
+    // [parts][4] and the status of one step of the last collected batch; kind 0 body, 1 face,
+    // 2 left hand, 3 right hand (an OPK_ERR_STATE error without views, batch or that extractor)
+    const float* keypoints_3d(int step, int kind, int* parts, int* status) const;
     // device scratch of the face / hand layers of a batch render (grows, never shrinks)
     void* part_render_scratch(int kind, size_t bytes) { return part_dev_[kind & 1].get(bytes); }
 
@@ -177,6 +189,19 @@ private:
     std::vector<std::vector<int64_t>> ids_;   // the collected batch's, per frame
     bool ids_valid_ = false;
     void run_tracker(const Slot& sl, int slot);
+    TriRig views_{};                  // views == 0: none
+    struct Array3d {
+        int parts = 0;                // 0: the kind was not run
+        std::vector<float> xyz;       // [steps][parts][4]
+        std::vector<int> status;      // [steps]
+    };
+    Array3d v3d_[4];
+    int v3d_steps_ = 0;
+    bool v3d_valid_ = false;
+    DevBuf v3d_dev_;
+    HostBuf v3d_host_;
+    void check_views(int n, int w, int h) const;   // the OPK_ERR_ARG of a submit against the rig
+    void run_views(const Slot& sl);
     struct NetOutput {
         const float* ptr;
         int h, w;
