@@ -215,6 +215,20 @@ class Frames:
         return out
 
 
+def _as_frames(frames, width=None, rows=False):
+    """`frames` as a Frames: a Frames as it is; the tensor form -- uint8 [n, h, w, 3], with `rows`
+    also [n, h, row bytes] of `width` pixels, a contiguous CUDA tensor -- as Frames.bgr of it."""
+    if isinstance(frames, Frames):
+        return frames
+    if rows:
+        _frame_rows(frames, width)
+    else:
+        n, h, w, c = frames.shape
+        assert c == 3 and frames.dtype == torch.uint8
+    _ptr(frames)
+    return Frames.bgr(frames, width)
+
+
 # Handles still open at interpreter exit (e.g. held by a test traceback) are closed before the HIP
 # runtime's own teardown: poses, then nets, then contexts.
 _LIVE = {"pose": weakref.WeakSet(), "extractor": weakref.WeakSet(), "tracker": weakref.WeakSet(),
@@ -363,18 +377,11 @@ class Context:
         net_input [n, 3, net_h, net_w] float32 (CUDA).  Frames with padded rows (a cv::Mat step)
         come as [n, h, row bytes] with `width` pixels per row; the frames may be a view that
         starts anywhere in a larger contiguous buffer (any base alignment).  Or a Frames."""
-        if isinstance(frames, Frames):
-            assert net_input.shape[0] == frames.n and net_input.shape[1] == 3
-            s = frames.struct()
-            check(self.L.opk_cvmat_to_input_fmt(self.h, _ptr(net_input), ctypes.byref(s),
-                                                float(scale), net_input.shape[3],
-                                                net_input.shape[2], normalize))
-            return
-        n, h, w, step = _frame_rows(frames, width)
-        assert net_input.shape[0] == n and net_input.shape[1] == 3
-        check(self.L.opk_cvmat_to_input(self.h, _ptr(net_input), _ptr(frames), n, w, h, step,
-                                        float(scale), net_input.shape[3], net_input.shape[2],
-                                        normalize))
+        frames = _as_frames(frames, width, rows=True)
+        assert net_input.shape[0] == frames.n and net_input.shape[1] == 3
+        s = frames.struct()
+        check(self.L.opk_cvmat_to_input_fmt(self.h, _ptr(net_input), ctypes.byref(s), float(scale),
+                                            net_input.shape[3], net_input.shape[2], normalize))
 
     def nms(self, peaks, heat, threshold=NMS_THRESHOLD, offset=(0.0, 0.0), semantics=MAPS_CPU):
         """peaks [N,parts,maxPeaks+1,3]; heat [N,C,H,W] (nmsGpu; semantics MAPS_CPU: nmsCpu's
@@ -441,20 +448,12 @@ class Context:
     def cvmat_to_output(self, frames, scale=1.0, out_size=None):
         """op::CvMatToOpOutput for a batch: frames [n, h, w, 3] uint8 BGR (CUDA) -> float32
         [n, out_h, out_w, 3]; out_size = (w, h), default the frames' own.  Or a Frames."""
-        if isinstance(frames, Frames):
-            ow, oh = out_size if out_size is not None else (frames.width, frames.height)
-            out = torch.empty((frames.n, max(oh, 0), max(ow, 0), 3), dtype=torch.float32,
-                              device=frames.device)
-            s = frames.struct()
-            check(self.L.opk_cvmat_to_output_fmt(self.h, _ptr(out), ctypes.byref(s), float(scale),
-                                                 ow, oh))
-            return out
-        n, h, w, c = frames.shape
-        assert c == 3 and frames.dtype == torch.uint8
-        ow, oh = out_size if out_size is not None else (w, h)
-        out = torch.empty((n, max(oh, 0), max(ow, 0), 3), dtype=torch.float32, device=frames.device)
-        check(self.L.opk_cvmat_to_output(self.h, _ptr(out), _ptr(frames), n, w, h, w * 3,
-                                         float(scale), ow, oh))
+        frames = _as_frames(frames)
+        ow, oh = out_size if out_size is not None else (frames.width, frames.height)
+        out = torch.empty((frames.n, max(oh, 0), max(ow, 0), 3), dtype=torch.float32,
+                          device=frames.device)
+        s = frames.struct()
+        check(self.L.opk_cvmat_to_output_fmt(self.h, _ptr(out), ctypes.byref(s), float(scale), ow, oh))
         return out
 
     def output_to_cvmat(self, output, cast=CAST_CPU, out=None):
@@ -477,13 +476,9 @@ class Context:
         Frames out: with a Frames as `out` (BGR, NV12 or I420), or out_format="nv12" | "i420",
         the drawn frames go there (opk_render_frames_to: Frames.from_bgr of the tensor result, bit
         for bit, converted inside the render) and that Frames is returned."""
-        fs = frames.struct() if isinstance(frames, Frames) else None
-        if fs is not None:
-            n, h, w = frames.n, frames.height, frames.width
-        else:
-            n, h, w, c = frames.shape
-            assert c == 3 and frames.dtype == torch.uint8
-        ow, oh = out_size if out_size is not None else (w, h)
+        frames = _as_frames(frames)
+        fs, n = frames.struct(), frames.n
+        ow, oh = out_size if out_size is not None else (frames.width, frames.height)
         dest = _frames_out(out, out_format, n, oh, ow, frames.device)
         if dest is None and out is None:
             out = torch.empty((n, max(oh, 0), max(ow, 0), 3), dtype=torch.uint8,
@@ -506,36 +501,17 @@ class Context:
             s.keypoints_dev = None if l.keypoints is None else _ptr(l.keypoints)
             s.counts_host = counts
             s.render_threshold, s.alpha, s.googly_eyes = l.threshold, l.alpha, int(l.googly_eyes)
+        hs = None if heat is None else ctypes.byref(self._heat_struct(heat, n))
         if dest is not None:
-            hs = None if heat is None else self._heat_struct(heat, n)
-            if fs is None:
-                fs = Frames.bgr(frames).struct()
             ds = dest.struct_out()
             check(self.L.opk_render_frames_to(self.h, ctypes.byref(ds), ctypes.byref(fs),
                                               float(scale), arr, len(layers), int(blend_original),
-                                              cast, None if hs is None else ctypes.byref(hs)))
+                                              cast, hs))
             return dest
-        if heat is None and fs is not None:
-            check(self.L.opk_render_frames_fmt(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow,
-                                               oh, ctypes.byref(fs), float(scale), arr,
-                                               len(layers), int(blend_original), cast))
-            return out
-        if heat is None:
-            check(self.L.opk_render_frames(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh,
-                                           _ptr(frames), n, w, h, w * 3, float(scale), arr,
-                                           len(layers), int(blend_original), cast))
-            return out
-        hs = self._heat_struct(heat, n)
-        if fs is not None:
-            check(self.L.opk_render_frames_heat_fmt(self.h, _ptr(out), _row_bytes(out, n, oh, ow),
-                                                    ow, oh, ctypes.byref(fs), float(scale), arr,
-                                                    len(layers), int(blend_original), cast,
-                                                    ctypes.byref(hs)))
-            return out
-        check(self.L.opk_render_frames_heat(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh,
-                                            _ptr(frames), n, w, h, w * 3, float(scale), arr,
-                                            len(layers), int(blend_original), cast,
-                                            ctypes.byref(hs)))
+        # (not through _to: that refuses a destination that overlaps its source; this form does not)
+        check(self.L.opk_render_frames_heat_fmt(self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow,
+                                                oh, ctypes.byref(fs), float(scale), arr, len(layers),
+                                                int(blend_original), cast, hs))
         return out
 
     @staticmethod
@@ -1359,23 +1335,18 @@ class PoseExtractor:
                                         float(dynamic_behavior), scale_number, float(scale_gap)))
 
     def _frames(self, fn, frames):
-        if isinstance(frames, Frames):
-            s = frames.struct()
-            check(getattr(self.L, fn.__name__ + "_fmt")(self.h, ctypes.byref(s)))
-            self._frames_n = frames.n
-            return
-        n, h, w, c = frames.shape
-        assert c == 3 and frames.dtype == torch.uint8
-        check(fn(self.h, _ptr(frames), n, w, h, w * 3))
-        self._frames_n = n
+        frames = _as_frames(frames)
+        s = frames.struct()
+        check(fn(self.h, ctypes.byref(s)))
+        self._frames_n = frames.n
 
     def forward_frames(self, frames):
         """Raw BGR uint8 frames [n, h, w, 3] (CUDA), or a Frames (BGR, NV12, I420): GPU
         preprocessing + net + post-processing."""
-        self._frames(self.L.opk_pose_forward_frames, frames)
+        self._frames(self.L.opk_pose_forward_frames_fmt, frames)
 
     def submit_frames(self, frames):
-        self._frames(self.L.opk_pose_submit_frames, frames)
+        self._frames(self.L.opk_pose_submit_frames_fmt, frames)
 
     def net_input_numpy(self, scale=0):
         p = ctypes.c_void_p()
@@ -1444,18 +1415,14 @@ class PoseExtractor:
         map / PAF of the batch instead, evaluated from the net output (no full-resolution stack
         is written), blended with alpha_heatmap.
         face / hands: also draw the attached extractors' results (attach) as a FACE and a HAND
-        layer after the POSE layer (opk_pose_render_frames_parts when the flags name every attached
+        layer after the POSE layer (opk_pose_render_frames_parts_fmt when the flags name every attached
         extractor; a subset is put together from the accessors and drawn by Context.render_frames,
         the same bytes).  frames may be a Frames (BGR, NV12 or I420).
         Frames out: a Frames as `out` (BGR, NV12 or I420), or out_format="nv12" | "i420", takes
         the drawn frames (opk_pose_render_frames_to) and is returned, as Context.render_frames."""
-        fs = frames.struct() if isinstance(frames, Frames) else None
-        if fs is not None:
-            n, h, w = frames.n, frames.height, frames.width
-        else:
-            n, h, w, c = frames.shape
-            assert c == 3 and frames.dtype == torch.uint8
-        ow, oh = out_size if out_size is not None else (w, h)
+        frames = _as_frames(frames)
+        fs, n = frames.struct(), frames.n
+        ow, oh = out_size if out_size is not None else (frames.width, frames.height)
         dest = _frames_out(out, out_format, n, oh, ow, frames.device)
         if dest is not None:
             out = dest
@@ -1469,8 +1436,6 @@ class PoseExtractor:
                 raise ValueError("no such extractor attached")
             every = bool(face) == (FACE in self._attached) and bool(hands) == (HAND in self._attached)
         if dest is not None and (every or not (face or hands)):
-            if fs is None:
-                fs = Frames.bgr(frames).struct()
             ds = dest.struct_out()
             parts = None
             if every:
@@ -1480,17 +1445,11 @@ class PoseExtractor:
                 alpha, alpha_heatmap, int(googly_eyes), int(blend_original), cast, parts))
             return dest
         if face or hands:
-            if every and fs is not None:
+            if every:   # every attached extractor's layer
                 check(self.L.opk_pose_render_frames_parts_fmt(
                     self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh, ctypes.byref(fs),
                     float(scale), threshold, alpha, int(googly_eyes), int(blend_original), cast,
                     face_threshold, face_alpha, hand_threshold, hand_alpha))
-                return out
-            if every:
-                check(self.L.opk_pose_render_frames_parts(   # every attached extractor's layer
-                    self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh, _ptr(frames), n, w, h,
-                    w * 3, float(scale), threshold, alpha, int(googly_eyes), int(blend_original),
-                    cast, face_threshold, face_alpha, hand_threshold, hand_alpha))
                 return out
             # a subset of the attached extractors: the same layers, put together here
             s = np.float32(scale)
@@ -1512,16 +1471,10 @@ class PoseExtractor:
                 layers.append(layer(LAYER_HAND, [self.hand_keypoints(f).reshape(-1, parts, 3)
                                                  for f in range(n)], 2, hand_threshold, hand_alpha))
             return self.ctx.render_frames(frames, layers, scale, out_size, blend_original, cast, out)
-        if fs is not None:
-            check(self.L.opk_pose_render_frames_element_fmt(
-                self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh, ctypes.byref(fs),
-                float(scale), int(element), threshold, alpha, alpha_heatmap, int(googly_eyes),
-                int(blend_original), cast))
-            return out
-        check(self.L.opk_pose_render_frames_element(
-            self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh, _ptr(frames), n, w, h, w * 3,
-            float(scale), int(element), threshold, alpha, alpha_heatmap, int(googly_eyes),
-            int(blend_original), cast))
+        check(self.L.opk_pose_render_frames_element_fmt(
+            self.h, _ptr(out), _row_bytes(out, n, oh, ow), ow, oh, ctypes.byref(fs), float(scale),
+            int(element), threshold, alpha, alpha_heatmap, int(googly_eyes), int(blend_original),
+            cast))
         return out
 
     def set_timing(self, on=True):
@@ -1690,10 +1643,7 @@ class KeypointExtractor:
         """frames: BGR uint8 [n, h, w, 3] CUDA tensor; rectangles [people, 4] (face) or
         [people, 2, 4] (hand); frame_of [people] or None.  Returns face [people, parts, 3] or
         hand [2, people, parts, 3] keypoints (numpy).  frames may be a Frames."""
-        fs = frames.struct() if isinstance(frames, Frames) else None
-        if fs is None:
-            n, h, w, c = frames.shape
-            assert c == 3 and frames.dtype == torch.uint8
+        fs = _as_frames(frames).struct()
         r = np.ascontiguousarray(rectangles, np.float32)
         people = r.shape[0]
         hands = 2 if self.kind == HAND else 1
@@ -1702,14 +1652,8 @@ class KeypointExtractor:
         if frame_of is not None:
             fo = np.ascontiguousarray(frame_of, np.int32)
             assert fo.shape == (people,)
-        if fs is not None:
-            check(self.L.opk_extractor_forward_fmt(
-                self.h, ctypes.byref(fs), r.ctypes.data_as(ctypes.c_void_p),
-                fo.ctypes.data_as(ctypes.c_void_p) if fo is not None else None, people,
-                out.ctypes.data_as(ctypes.c_void_p)))
-            return out[0] if self.kind == FACE else out
-        check(self.L.opk_extractor_forward(
-            self.h, _ptr(frames), n, w, h, w * 3, r.ctypes.data_as(ctypes.c_void_p),
+        check(self.L.opk_extractor_forward_fmt(
+            self.h, ctypes.byref(fs), r.ctypes.data_as(ctypes.c_void_p),
             fo.ctypes.data_as(ctypes.c_void_p) if fo is not None else None, people,
             out.ctypes.data_as(ctypes.c_void_p)))
         return out[0] if self.kind == FACE else out

@@ -556,70 +556,120 @@ int opk_pose_forward_frames(opk_pose* p, const uint8_t* frames, int n, int width
 
 namespace {
 
-// The three pose renders on a resolved destination (BGR: the entry points below; any format:
+// The pose renders on a resolved destination (BGR: the entry points below; any format:
 // opk_pose_render_frames_to), inside guarded_net.
-void pose_render_keypoints(opk_pose* p, const opk::FrameDest& dst, const opk::FrameSource& src,
-                           double scale, float threshold, float alpha, int googly_eyes,
-                           int blend_original, int cast)
+
+// the collected batch is the n frames about to be drawn
+void check_batch(const opk::PoseHip& pose, int n)
 {
-    const int n = src.n;
-    std::vector<int> counts;
-    opk_render_layer layer{};
-    const opk::PoseHip& pose = *p->pose;
     if (pose.frames() == 0) throw opk::Error(OPK_ERR_STATE, "no collected batch to render");
     if (n != pose.frames())
         throw opk::Error(OPK_ERR_STATE, "the collected batch has " +
                                             std::to_string(pose.frames()) + " frames, not " +
                                             std::to_string(n));
-    const int parts = opk::pose_model(pose.model()).parts;
-    std::vector<float> kp;
-    for (int f = 0; f < n; ++f) {
-        const int people = pose.num_people(f);
-        counts.push_back(people);
-        const auto& k = pose.keypoints(f);
-        kp.insert(kp.end(), k.begin(), k.begin() + (size_t)people * parts * 3);
-    }
-    // scaleKeypoints: x and y times scaleInputToOutput, in float
+}
+
+// scaleKeypoints: x and y times scaleInputToOutput, in float
+void scale_keypoints(std::vector<float>& kp, double scale)
+{
     const float s = (float)scale;
     if (s != 1.f)
         for (size_t i = 0; i < kp.size(); i += 3) {
             kp[i] *= s;
             kp[i + 1] *= s;
         }
-    layer.kind = OPK_LAYER_POSE;
-    layer.pose_model = pose.model();
-    layer.counts_host = counts.data();
-    layer.render_threshold = threshold;
-    layer.alpha = alpha;
-    layer.googly_eyes = googly_eyes;
-    opk::render_frames(p->ctx, dst, src, scale, &layer, 1, blend_original, cast, kp.data(),
-                       kp.size());
 }
 
-void pose_render_element(opk_pose* p, const opk::FrameDest& dst, const opk::FrameSource& src,
-                         double scale, int element, float threshold, float alpha_keypoint,
-                         float alpha_heatmap, int googly_eyes, int blend_original, int cast)
+// The keypoints of the collected batch drawn on its frames: the POSE layer and, with `part`
+// ({face threshold, face alpha, hand threshold, hand alpha}; NULL: none), a layer for every
+// attached extractor
+void pose_render_keypoints(opk_pose* p, const opk::FrameDest& dst, const opk::FrameSource& src,
+                           double scale, float threshold, float alpha, int googly_eyes,
+                           int blend_original, int cast, const float* part = nullptr)
 {
-    if (element == 0) {
-        pose_render_keypoints(p, dst, src, scale, threshold, alpha_keypoint, googly_eyes,
-                              blend_original, cast);
-        return;
-    }
     const int n = src.n;
+    opk::PoseHip& pose = *p->pose;
+    check_batch(pose, n);
+    const int parts = opk::pose_model(pose.model()).parts;
+    std::vector<int> counts[3];
+    std::vector<float> kp[3];
+    opk_render_layer layers[3] = {};
+    int nl = 0;
+    for (int f = 0; f < n; ++f) {
+        const int people = pose.num_people(f);
+        counts[0].push_back(people);
+        const auto& k = pose.keypoints(f);
+        kp[0].insert(kp[0].end(), k.begin(), k.begin() + (size_t)people * parts * 3);
+    }
+    scale_keypoints(kp[0], scale);
+    layers[nl].kind = OPK_LAYER_POSE;
+    layers[nl].pose_model = pose.model();
+    layers[nl].counts_host = counts[0].data();
+    layers[nl].render_threshold = threshold;
+    layers[nl].alpha = alpha;
+    layers[nl].googly_eyes = googly_eyes;
+    ++nl;
+    for (int kind = 0; part && kind < 2; ++kind) {
+        if (!pose.attached(kind)) continue;
+        p->ctx->bind();
+        const bool hand = kind == OPK_EXTRACT_HAND;
+        const int hands = hand ? 2 : 1;
+        std::vector<float>& v = kp[1 + kind];
+        for (int f = 0; f < n; ++f) {   // a frame's left hands, then its right hands
+            int first = 0, total = 0, P = 0;
+            const float* all = pose.part_keypoints(kind, f, &first, &total, &P);
+            const int people = pose.num_people(f);
+            counts[1 + kind].push_back(hands * people);
+            for (int hd = 0; hd < hands; ++hd) {
+                const float* q = all + ((size_t)hd * total + first) * P * 3;
+                v.insert(v.end(), q, q + (size_t)people * P * 3);
+            }
+        }
+        scale_keypoints(v, scale);
+        float* dev = static_cast<float*>(
+            pose.part_render_scratch(kind, std::max<size_t>(1, v.size()) * sizeof(float)));
+        if (!v.empty()) {
+            OPK_HIP(hipMemcpyAsync(dev, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice,
+                                   p->ctx->stream));
+            OPK_HIP(hipStreamSynchronize(p->ctx->stream));   // `v` is pageable
+        }
+        layers[nl].kind = hand ? OPK_LAYER_HAND : OPK_LAYER_FACE;
+        layers[nl].keypoints_dev = dev;
+        layers[nl].counts_host = counts[1 + kind].data();
+        layers[nl].render_threshold = part[hand ? 2 : 0];
+        layers[nl].alpha = part[hand ? 3 : 1];
+        ++nl;
+    }
+    opk::render_frames(p->ctx, dst, src, scale, layers, nl, blend_original, cast, kp[0].data(),
+                       kp[0].size());
+}
+
+// one element of --part_to_show other than the keypoints (element 0: pose_render_keypoints)
+void pose_render_heat(opk_pose* p, const opk::FrameDest& dst, const opk::FrameSource& src,
+                      double scale, int element, float alpha_heatmap, int blend_original, int cast)
+{
     const opk::PoseHip& pose = *p->pose;
     opk_render_heat heat{};
     heat.pose_model = pose.model();
     opk::render_element(pose.model(), element, &heat.kind, &heat.channel);
-    if (pose.frames() == 0) throw opk::Error(OPK_ERR_STATE, "no collected batch to render");
-    if (n != pose.frames())
-        throw opk::Error(OPK_ERR_STATE, "the collected batch has " + std::to_string(pose.frames()) +
-                                            " frames, not " + std::to_string(n));
+    check_batch(pose, src.n);
     const opk::HeatMap& lazy = pose.lazy_heat();
     // renderPose: scaleNetToOutput * scaleInputToOutput, both float; "no blending" is alpha 1,
     // so the frame is never cleared
     heat.scale_to_keep_ratio = pose.scale_net_to_output() * (float)scale;
     heat.alpha = blend_original ? alpha_heatmap : 1.f;
     opk::render_frames(p->ctx, dst, src, scale, nullptr, 0, 1, cast, nullptr, 0, &heat, &lazy);
+}
+
+void pose_render_element(opk_pose* p, const opk::FrameDest& dst, const opk::FrameSource& src,
+                         double scale, int element, float threshold, float alpha_keypoint,
+                         float alpha_heatmap, int googly_eyes, int blend_original, int cast)
+{
+    if (element == 0)
+        pose_render_keypoints(p, dst, src, scale, threshold, alpha_keypoint, googly_eyes,
+                              blend_original, cast);
+    else
+        pose_render_heat(p, dst, src, scale, element, alpha_heatmap, blend_original, cast);
 }
 
 }  // namespace
@@ -878,87 +928,6 @@ int opk_pose_read_part_times(opk_pose* p, int kind, int* batches, int* crops, do
     });
 }
 
-}  // extern "C"
-
-namespace {
-
-void pose_render_parts(opk_pose* p, const opk::FrameDest& dst, const opk::FrameSource& src,
-                       double scale, float threshold, float alpha, int googly_eyes,
-                       int blend_original, int cast, float face_threshold, float face_alpha,
-                       float hand_threshold, float hand_alpha)
-{
-    const int n = src.n;
-    opk::PoseHip& pose = *p->pose;
-    if (pose.frames() == 0) throw opk::Error(OPK_ERR_STATE, "no collected batch to render");
-    if (n != pose.frames())
-        throw opk::Error(OPK_ERR_STATE, "the collected batch has " +
-                                            std::to_string(pose.frames()) + " frames, not " +
-                                            std::to_string(n));
-    const float s = (float)scale;   // scaleKeypoints: x and y times scaleInputToOutput, in float
-    auto scaled = [s](std::vector<float>& kp) {
-        if (s != 1.f)
-            for (size_t i = 0; i < kp.size(); i += 3) {
-                kp[i] *= s;
-                kp[i + 1] *= s;
-            }
-    };
-    const int parts = opk::pose_model(pose.model()).parts;
-    std::vector<int> counts[3];
-    std::vector<float> kp[3];
-    opk_render_layer layers[3] = {};
-    int nl = 0;
-    for (int f = 0; f < n; ++f) {
-        const int people = pose.num_people(f);
-        counts[0].push_back(people);
-        const auto& k = pose.keypoints(f);
-        kp[0].insert(kp[0].end(), k.begin(), k.begin() + (size_t)people * parts * 3);
-    }
-    scaled(kp[0]);
-    layers[nl].kind = OPK_LAYER_POSE;
-    layers[nl].pose_model = pose.model();
-    layers[nl].counts_host = counts[0].data();
-    layers[nl].render_threshold = threshold;
-    layers[nl].alpha = alpha;
-    layers[nl].googly_eyes = googly_eyes;
-    ++nl;
-    p->ctx->bind();
-    for (int kind = 0; kind < 2; ++kind) {
-        if (!pose.attached(kind)) continue;
-        const int hands = kind == OPK_EXTRACT_HAND ? 2 : 1;
-        std::vector<float>& v = kp[1 + kind];
-        for (int f = 0; f < n; ++f) {   // a frame's left hands, then its right hands
-            int first = 0, total = 0, P = 0;
-            const float* src = pose.part_keypoints(kind, f, &first, &total, &P);
-            const int people = pose.num_people(f);
-            counts[1 + kind].push_back(hands * people);
-            for (int hd = 0; hd < hands; ++hd) {
-                const float* q = src + ((size_t)hd * total + first) * P * 3;
-                v.insert(v.end(), q, q + (size_t)people * P * 3);
-            }
-        }
-        scaled(v);
-        float* dev = static_cast<float*>(
-            pose.part_render_scratch(kind, std::max<size_t>(1, v.size()) * sizeof(float)));
-        if (!v.empty()) {
-            OPK_HIP(hipMemcpyAsync(dev, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice,
-                                   p->ctx->stream));
-            OPK_HIP(hipStreamSynchronize(p->ctx->stream));   // `v` is pageable
-        }
-        layers[nl].kind = kind == OPK_EXTRACT_HAND ? OPK_LAYER_HAND : OPK_LAYER_FACE;
-        layers[nl].keypoints_dev = dev;
-        layers[nl].counts_host = counts[1 + kind].data();
-        layers[nl].render_threshold = kind == OPK_EXTRACT_HAND ? hand_threshold : face_threshold;
-        layers[nl].alpha = kind == OPK_EXTRACT_HAND ? hand_alpha : face_alpha;
-        ++nl;
-    }
-    opk::render_frames(p->ctx, dst, src, scale, layers, nl, blend_original, cast,
-                       kp[0].data(), kp[0].size());
-}
-
-}  // namespace
-
-extern "C" {
-
 int opk_pose_render_frames_parts_fmt(opk_pose* p, uint8_t* dst, size_t dst_step, int out_w,
                                      int out_h, const opk_frames* frames, double scale,
                                      float threshold, float alpha, int googly_eyes,
@@ -969,9 +938,9 @@ int opk_pose_render_frames_parts_fmt(opk_pose* p, uint8_t* dst, size_t dst_step,
         OPK_CHECK_ARG(p, "NULL pose");
         OPK_CHECK_ARG(frames, "NULL frames");
         const opk::FrameSource src = opk::frame_source(*frames);
-        pose_render_parts(p, opk::bgr_dest(dst, dst_step, src.n, out_w, out_h), src, scale,
-                          threshold, alpha, googly_eyes, blend_original, cast, face_threshold,
-                          face_alpha, hand_threshold, hand_alpha);
+        const float part[4] = {face_threshold, face_alpha, hand_threshold, hand_alpha};
+        pose_render_keypoints(p, opk::bgr_dest(dst, dst_step, src.n, out_w, out_h), src, scale,
+                              threshold, alpha, googly_eyes, blend_original, cast, part);
     });
 }
 
@@ -992,8 +961,8 @@ int opk_pose_render_frames_to(opk_pose* p, const opk_frames_out* dst, const opk_
             return;
         }
         OPK_CHECK_ARG(element == 0, "face / hand layers are drawn with the keypoints (element 0)");
-        pose_render_parts(p, d, src, scale, threshold, alpha_keypoint, googly_eyes, blend_original,
-                          cast, part_params[0], part_params[1], part_params[2], part_params[3]);
+        pose_render_keypoints(p, d, src, scale, threshold, alpha_keypoint, googly_eyes,
+                              blend_original, cast, part_params);
     });
 }
 

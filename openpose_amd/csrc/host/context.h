@@ -88,7 +88,7 @@ struct Context {
 // heat (may be NULL): the heat layer of opk_render_frames_heat; with `lazy` its values come from
 // that map instead of heat->heat_dev (opk_pose_render_frames_element), whose size fields it sets.
 // dst: where the drawn frames go, out_w x out_h = dst.w x dst.h -- bgr_dest() of the BGR entry
-// points, or a checked opk_frames_out (frame_dest(), host/input.h) of the `_to` ones.
+// points, or a checked opk_frames_out (frame_dest(), host/frames.h) of the `_to` ones.
 void render_frames(Context* ctx, const FrameDest& dst, const FrameSource& frames, double scale, const ::opk_render_layer* layers,
                    int n_layers, int blend_original, int cast,
                    const float* kp_host = nullptr, size_t kp_floats = 0,

@@ -176,82 +176,6 @@ const Context::WarpAxes& Context::warp_axis_tables(double scale, int dw, int dh)
     return ref;
 }
 
-FrameSource frame_source(const ::opk_frames& d)
-{
-    static_assert(OPK_FRAMES_BGR == kFramesBgr && OPK_FRAMES_NV12 == kFramesNv12 &&
-                      OPK_FRAMES_I420 == kFramesI420,
-                  "OPK_FRAMES_* are FrameFormat's values");
-    OPK_CHECK_ARG(d.format == OPK_FRAMES_BGR || d.format == OPK_FRAMES_NV12 ||
-                      d.format == OPK_FRAMES_I420,
-                  "unknown frame format: OPK_FRAMES_BGR (0), OPK_FRAMES_NV12 (1) or OPK_FRAMES_I420 (2)");
-    OPK_CHECK_ARG(d.n >= 0, "negative frame count");
-    FrameSource s{};
-    s.format = d.format;
-    s.n = d.n;
-    s.w = d.width;
-    s.h = d.height;
-    const size_t w = d.width > 0 ? (size_t)d.width : 0, h = d.height > 0 ? (size_t)d.height : 0;
-    if (d.format == OPK_FRAMES_BGR) {
-        OPK_CHECK_ARG(d.step[0] == 0 || d.step[0] >= w * 3, "row step shorter than the row");
-        s.plane[0] = d.plane[0];
-        s.step = d.step[0] ? d.step[0] : w * 3;
-        s.frame[0] = d.frame_bytes[0] ? d.frame_bytes[0] : s.step * h;
-        return s;
-    }
-    OPK_CHECK_ARG(d.width % 2 == 0 && d.height % 2 == 0,
-                  "YUV 4:2:0 frames need an even width and height");
-    const bool nv12 = d.format == OPK_FRAMES_NV12;
-    const size_t crow = nv12 ? w : w / 2;   // bytes of a chroma row
-    OPK_CHECK_ARG(d.step[0] == 0 || d.step[0] >= w, "row step shorter than the row");
-    OPK_CHECK_ARG(d.step[1] == 0 || d.step[1] >= crow, "row step shorter than the row");
-    OPK_CHECK_ARG(nv12 || d.step[2] == 0 || d.step[2] >= crow, "row step shorter than the row");
-    if (d.n > 0)
-        OPK_CHECK_ARG(d.plane[0] && d.plane[1] && (nv12 || d.plane[2]),
-                      nv12 ? "NULL plane: NV12 frames need plane[0] (Y) and plane[1] (UV)"
-                           : "NULL plane: I420 frames need plane[0] (Y), plane[1] (U) and plane[2] (V)");
-    s.step = d.step[0] ? d.step[0] : w;
-    s.cstep = d.step[1] ? d.step[1] : crow;
-    OPK_CHECK_ARG(nv12 || (d.step[2] ? d.step[2] : crow) == s.cstep,
-                  "the U and V planes of I420 frames share one row step");
-    s.cpix = nv12 ? 2 : 1;
-    s.plane[0] = d.plane[0];
-    s.plane[1] = d.plane[1];
-    s.plane[2] = nv12 ? (d.plane[1] ? d.plane[1] + 1 : nullptr) : d.plane[2];
-    s.frame[0] = d.frame_bytes[0] ? d.frame_bytes[0] : s.step * h;
-    s.frame[1] = d.frame_bytes[1] ? d.frame_bytes[1] : s.cstep * (h / 2);
-    s.frame[2] = nv12 ? s.frame[1] : (d.frame_bytes[2] ? d.frame_bytes[2] : s.cstep * (h / 2));
-    return s;
-}
-
-FrameDest frame_dest(const ::opk_frames_out& d)
-{
-    // the same fields with writable planes: the same checks and defaults
-    ::opk_frames in{};
-    in.format = d.format;
-    in.n = d.n;
-    in.width = d.width;
-    in.height = d.height;
-    for (int i = 0; i < 3; ++i) {
-        in.plane[i] = d.plane[i];
-        in.step[i] = d.step[i];
-        in.frame_bytes[i] = d.frame_bytes[i];
-    }
-    const FrameSource s = frame_source(in);
-    FrameDest o{};
-    o.format = s.format;
-    o.n = s.n;
-    o.w = s.w;
-    o.h = s.h;
-    o.step = s.step;
-    o.cstep = s.cstep;
-    o.cpix = s.cpix;
-    for (int i = 0; i < 3; ++i) {
-        o.plane[i] = const_cast<uint8_t*>(s.plane[i]);
-        o.frame[i] = s.frame[i];
-    }
-    return o;
-}
-
 void check_frames_apart(const FrameDest& dst, const FrameSource& src)
 {
     // every plane of every frame as the byte range [first sample, one past its last]; NV12's pairs
@@ -269,24 +193,23 @@ void check_frames_apart(const FrameDest& dst, const FrameSource& src)
             ranges.push_back(Range{lo, lo + (rows - 1) * step + row, is_dst});
         }
     };
-    auto planes = [&](int format, const uint8_t* const* plane, const size_t* frame, size_t step,
-                      size_t cstep, int n, int w, int h, bool is_dst) {
-        if (w <= 0 || h <= 0) return;
-        if (format == kFramesBgr) {
-            add(plane[0], frame[0], step, (size_t)h, (size_t)w * 3, n, is_dst);
+    auto planes = [&](const auto& f, bool is_dst) {
+        if (f.w <= 0 || f.h <= 0) return;
+        const size_t w = (size_t)f.w, h = (size_t)f.h;
+        if (f.format == kFramesBgr) {
+            add(f.plane[0], f.frame[0], f.step, h, w * 3, f.n, is_dst);
             return;
         }
-        add(plane[0], frame[0], step, (size_t)h, (size_t)w, n, is_dst);
-        if (format == kFramesNv12) {
-            add(plane[1], frame[1], cstep, (size_t)h / 2, (size_t)w, n, is_dst);
+        add(f.plane[0], f.frame[0], f.step, h, w, f.n, is_dst);
+        if (f.format == kFramesNv12) {
+            add(f.plane[1], f.frame[1], f.cstep, h / 2, w, f.n, is_dst);
         } else {
-            add(plane[1], frame[1], cstep, (size_t)h / 2, (size_t)w / 2, n, is_dst);
-            add(plane[2], frame[2], cstep, (size_t)h / 2, (size_t)w / 2, n, is_dst);
+            add(f.plane[1], f.frame[1], f.cstep, h / 2, w / 2, f.n, is_dst);
+            add(f.plane[2], f.frame[2], f.cstep, h / 2, w / 2, f.n, is_dst);
         }
     };
-    const uint8_t* dp[3] = {dst.plane[0], dst.plane[1], dst.plane[2]};
-    planes(dst.format, dp, dst.frame, dst.step, dst.cstep, dst.n, dst.w, dst.h, true);
-    planes(src.format, src.plane, src.frame, src.step, src.cstep, src.n, src.w, src.h, false);
+    planes(dst, true);
+    planes(src, false);
     std::sort(ranges.begin(), ranges.end(), [](const Range& a, const Range& b) { return a.lo < b.lo; });
     uintptr_t dst_end = 0, src_end = 0;
     for (const Range& r : ranges) {

@@ -6,6 +6,7 @@
 
 #include "../../../include/opk.h"
 #include "../kernels/kernels.h"
+#include "frames.h"
 
 namespace opk {
 
@@ -25,12 +26,7 @@ void scale_and_size(int in_w, int in_h, int net_w, int net_h, float dyn, int sca
 void warp_weight_table(bool cubic, short* itab);
 void warp_axis_table(double scale, int d, bool cubic, int* tab /* 2*d */);
 
-// An opk_frames descriptor (include/opk.h) checked and resolved, before any device work: unknown
-// format, n < 0, a step shorter than its row, and for NV12 / I420 an odd width or height and (n > 0)
-// a NULL plane are OPK_ERR_ARG; steps and frame strides of 0 get their tight values, NV12's V plane
-// is U + 1.  Sizes <= 0 and a NULL BGR buffer are left to the callers' own checks, which the
-// pointer-taking entry points share.  The result holds no pointer into the descriptor.
-FrameSource frame_source(const ::opk_frames& frames);
+// (frame_source() / frame_dest(), the checked and resolved descriptors: frames.h)
 // the descriptor the pointer-taking entry points fill: n BGR frames [height][step bytes]
 inline ::opk_frames bgr_descriptor(const uint8_t* frames, int n, int width, int height, size_t step)
 {
@@ -44,8 +40,6 @@ inline ::opk_frames bgr_descriptor(const uint8_t* frames, int n, int width, int 
     return d;
 }
 
-// An opk_frames_out descriptor checked and resolved exactly as frame_source does its twin
-FrameDest frame_dest(const ::opk_frames_out& frames);
 // the BGR destination the pointer-taking render entry points describe: n frames [out_h][step bytes]
 // (step 0 stays 0 here: render_frames checks it against the row and then takes the tight value)
 inline FrameDest bgr_dest(uint8_t* dst, size_t step, int n, int out_w, int out_h)

@@ -155,7 +155,7 @@ namespace {
 
 // ---- the output image (CvMatToOpOutput, OpOutputToCvMat) and the fused batch render -------------
 
-// (the frames' own checks -- format, steps, planes -- are frame_source's, host/input.cpp)
+// (the frames' own checks -- format, steps, planes -- are frame_source's, host/frames.h)
 void check_output_sizes(int width, int height, int out_w, int out_h, double scale)
 {
     // CvMatToOpOutput::createArray's sanity checks (cvMatToOpOutput.cpp:87-90)

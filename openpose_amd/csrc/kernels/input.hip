@@ -14,6 +14,7 @@
 #include "kernels.h"
 #include "warp_dev.h"
 #include "../common.h"
+#include "../host/frames.h"
 
 namespace opk {
 
@@ -132,7 +133,7 @@ void launch_cvmat_to_input(float* dst, const FrameSource& fs, int n, int dh, int
     }
     const uint8_t* src = fs.plane[0];
     const size_t src_step = fs.step, frame = fs.frame[0];
-    OPK_CHECK_ARG(src_step >= (size_t)sw * 3, "row step shorter than the row");
+    check_frames(fs);
     const dim3 grid((unsigned)(n * dh));
     const int threads = dw >= 256 ? 256 : (dw >= 128 ? 128 : 64);
     const auto* xt = reinterpret_cast<const int2*>(xtab);
@@ -142,7 +143,7 @@ void launch_cvmat_to_input(float* dst, const FrameSource& fs, int n, int dh, int
     const size_t rows_at = ((size_t)dw * 8 + 64 * ksize * ksize + 15) & ~(size_t)15;
     const size_t lds = rows_at + (size_t)ksize * lds_row;   // x table, weight sets, source rows
     if (lds <= 64 * 1024) {
-        const bool a16 = ((uintptr_t)src % 16 == 0) && src_step % 16 == 0 && frame % 16 == 0;
+        const bool a16 = frames_aligned(fs, 16);
 #define OPK_WARP_LDS(K_, A_)                                                                   \
     hipLaunchKernelGGL((cvmat_to_input_lds_kernel<K_, A_>), grid, dim3(threads), lds, stream, dst, \
                        src, sh, sw, src_step, frame, dh, dw, xt, yt, wtab, normalize, frame_of,  \

@@ -86,25 +86,20 @@ size_t paf_staged_bytes(const HeatMap& heat);
 // n uint8 frames of w x h pixels on the device, packed BGR or YUV 4:2:0.  One description serves
 // NV12 and I420: the chroma sample of luma pixel (x, y) of frame f is
 // plane[1 | 2][f * frame[1 | 2] + (y >> 1) * cstep + (x >> 1) * cpix].
+// B is the byte type of the planes: const where frames are read (FrameSource), writable where
+// drawn or converted frames go (FrameDest, opk_frames_out).  A kernel argument: the layout is fixed.
 enum FrameFormat { kFramesBgr = 0, kFramesNv12 = 1, kFramesI420 = 2 };
-struct FrameSource {
-    int format;                // FrameFormat
+template <class B>
+struct FramesT {
+    int format;            // FrameFormat
     int n, w, h;
-    const uint8_t* plane[3];   // frame 0 -- BGR: [0]; YUV: Y, U, V (NV12: V = U + 1)
-    size_t step, cstep;        // row bytes of plane[0] (BGR or luma) and of the chroma rows
-    size_t frame[3];           // bytes from frame f to f + 1 of each plane
-    int cpix;                  // bytes from one chroma sample to the next: 2 NV12, 1 I420
+    B* plane[3];           // frame 0 -- BGR: [0]; YUV: Y, U, V (NV12: V = U + 1)
+    size_t step, cstep;    // row bytes of plane[0] (BGR or luma) and of the chroma rows
+    size_t frame[3];       // bytes from frame f to f + 1 of each plane
+    int cpix;              // bytes from one chroma sample to the next: 2 NV12, 1 I420
 };
-
-// The same description with writable planes: where drawn or converted frames go (opk_frames_out)
-struct FrameDest {
-    int format;
-    int n, w, h;
-    uint8_t* plane[3];
-    size_t step, cstep;
-    size_t frame[3];
-    int cpix;
-};
+using FrameSource = FramesT<const uint8_t>;
+using FrameDest = FramesT<uint8_t>;
 
 // ---- YUV 4:2:0 -> BGR (yuv.hip; the arithmetic: yuv_dev.h) -------------------------------------
 // dst BGR uint8 [src.n][src.h][dst_step] (only w*3 bytes of a row are written) from NV12 / I420

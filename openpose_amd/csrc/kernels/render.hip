@@ -35,6 +35,7 @@
 #include "yuv_dev.h"
 #include "yuv_out_dev.h"
 #include "../common.h"
+#include "../host/frames.h"
 
 #include <cmath>
 
@@ -43,6 +44,7 @@ namespace opk {
 namespace {
 
 constexpr int kTileW = 32, kTileH = 8;
+static_assert(kTileW == kYuvTileW && kTileH == kYuvTileH, "yuv_store_tile stages the render's tile");
 // float(pi) as renderPose.cu:10's __constant__ PI rounds
 constexpr float kPi = 3.14159265358979323846f;
 
@@ -905,77 +907,16 @@ __global__ __launch_bounds__(256) void render_frames_kernel(const RenderFramesAr
     const unsigned cb = cast_u8(b, a.cast), cg = cast_u8(g, a.cast), cr = cast_u8(r, a.cast);
     const int tx0 = blockIdx.x * kTileW, ty0 = blockIdx.y * kTileH;
     const int rows = min(kTileH, a.h - ty0), cols = min(kTileW, a.w - tx0);
-    // 5. an NV12 / I420 destination: the cast bytes become samples here (yuv_out_dev.h) -- every
-    //    lane its pixel's luma, the lanes at even (x, y) their block's (U, V); w and h are even, so
-    //    a block lies inside the frame, and the tile, with its top-left
+    // 5. an NV12 / I420 destination: the cast bytes become samples and leave (yuv_out_dev.h);
+    //    `items` is idle -- every use of it ended at a barrier -- and stages the tile
     if constexpr (YuvOut) {
-        const unsigned Y = bgr_to_y((int)cb, (int)cg, (int)cr);
-        const bool top = ((t.x | t.y) & 1) == 0;
-        const unsigned U = bgr_to_u((int)cb, (int)cg, (int)cr);
-        const unsigned V = bgr_to_v((int)cb, (int)cg, (int)cr);
-        const int cpix = a.out.cpix;
-        if (!a.dst_aligned) {
-            if (t.inside) {
-                const YuvOutRow o = yuv_out_row(a.out, f, t.y);
-                o.y[t.x] = (uint8_t)Y;
-                if (top) {
-                    o.u[(t.x >> 1) * cpix] = (uint8_t)U;
-                    o.v[(t.x >> 1) * cpix] = (uint8_t)V;
-                }
-            }
-            return;
-        }
-        // every plane on 4-byte boundaries (a tile starts at byte 32 * blockIdx.x of its luma and
-        // NV12 chroma rows, 16 * blockIdx.x of its I420 ones): the tile's 8 x 32 luma bytes and
-        // 4 x 32 chroma bytes (NV12: pairs; I420: 16 of U at 256, 16 of V at 320 per row) go through
-        // LDS and leave as 4-byte stores: wave 0 the luma, 8 lanes a row; wave 1 the chroma,
-        // 8 (NV12) or 4 + 4 (I420) lanes a row; what a row has left over as bytes
-        uint8_t* stage = reinterpret_cast<uint8_t*>(items);
-        const int lx = threadIdx.x & (kTileW - 1), ly = threadIdx.x / kTileW;
-        stage[threadIdx.x] = (uint8_t)Y;
-        if (top) {
-            if (cpix == 2) {
-                stage[256 + (ly >> 1) * 32 + lx] = (uint8_t)U;
-                stage[256 + (ly >> 1) * 32 + lx + 1] = (uint8_t)V;
-            } else {
-                stage[256 + (ly >> 1) * 16 + (lx >> 1)] = (uint8_t)U;
-                stage[320 + (ly >> 1) * 16 + (lx >> 1)] = (uint8_t)V;
-            }
-        }
-        __syncthreads();
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        if (wave > 1) return;
-        uint8_t* d;
-        const uint8_t* s;
-        int left;   // bytes of the row from this lane's first
-        if (wave == 0) {
-            const int row = lane >> 3, o = (lane & 7) * 4;
-            if (row >= rows) return;
-            d = a.out.plane[0] + (size_t)f * a.out.frame[0] + (size_t)(ty0 + row) * a.out.step + tx0 + o;
-            s = stage + row * 32 + o;
-            left = cols - o;
-        } else if (cpix == 2) {
-            const int row = lane >> 3, o = (lane & 7) * 4;
-            if (lane >= 32 || 2 * row >= rows) return;
-            d = a.out.plane[1] + (size_t)f * a.out.frame[1] + (size_t)((ty0 >> 1) + row) * a.out.cstep +
-                tx0 + o;
-            s = stage + 256 + row * 32 + o;
-            left = cols - o;
-        } else {
-            const int p = lane >> 4, row = (lane >> 2) & 3, o = (lane & 3) * 4;   // p: U, V
-            if (lane >= 32 || 2 * row >= rows) return;
-            d = a.out.plane[1 + p] + (size_t)f * a.out.frame[1 + p] +
-                (size_t)((ty0 >> 1) + row) * a.out.cstep + (tx0 >> 1) + o;
-            s = stage + 256 + p * 64 + row * 16 + o;
-            left = (cols >> 1) - o;
-        }
-        if (left >= 4) {
-            *reinterpret_cast<unsigned*>(d) = *reinterpret_cast<const unsigned*>(s);
-        } else {
-            for (int i = 0; i < left; ++i) d[i] = s[i];
-        }
+        yuv_store_tile(a, f, t.x, t.y, t.inside, cb, cg, cr, reinterpret_cast<uint8_t*>(items),
+                       threadIdx.x, tx0, ty0, rows, cols);
         return;
     }
+    // 6. a BGR destination.  (Written out here, not a helper like step 5: as a function of its own
+    //    these lines are optimised before they are inlined -- the lane's / 24 and % 24 come out 16
+    //    bits wide -- and all 24 BGR kernels become other code, which nothing here has measured.)
     if (!a.dst_aligned) {
         if (t.inside) {
             uint8_t* d = a.dst + (size_t)f * a.dst_frame + (size_t)t.y * a.dst_step + (size_t)t.x * 3;
@@ -1050,16 +991,7 @@ void check_warp(const FrameWarp& wp, int w, int h)
 {
     const FrameSource& fs = wp.src;
     OPK_CHECK_ARG(fs.plane[0] && fs.w > 0 && fs.h > 0, "empty frame");
-    if (fs.format == kFramesBgr) {
-        OPK_CHECK_ARG(fs.step >= (size_t)fs.w * 3, "row step shorter than the row");
-    } else {
-        OPK_CHECK_ARG(fs.format == kFramesNv12 || fs.format == kFramesI420, "unknown frame format");
-        OPK_CHECK_ARG(fs.w % 2 == 0 && fs.h % 2 == 0, "YUV 4:2:0 frames have even width and height");
-        OPK_CHECK_ARG(fs.plane[1] && fs.plane[2], "NULL plane");
-        OPK_CHECK_ARG(fs.cpix == (fs.format == kFramesNv12 ? 2 : 1), "chroma sample stride");
-        OPK_CHECK_ARG(fs.step >= (size_t)fs.w && fs.cstep >= (size_t)(fs.w / 2) * fs.cpix,
-                      "row step shorter than the row");
-    }
+    check_frames(fs);
     OPK_CHECK_ARG(wp.ksize == 0 || wp.ksize == 2 || wp.ksize == 4, "copy, linear or cubic");
     OPK_CHECK_ARG(wp.ksize != 0 || (w == fs.w && h == fs.h), "a copy keeps the size");
     OPK_CHECK_ARG(wp.ksize == 0 || (wp.xtab && wp.ytab && wp.wtab), "NULL warp table");
@@ -1122,22 +1054,9 @@ void launch_render_frames(const RenderFramesArgs& args, hipStream_t stream)
     FrameDest& D = a.out;
     OPK_CHECK_ARG(D.plane[0] && a.n > 0 && a.w > 0 && a.h > 0, "empty output image");
     OPK_CHECK_ARG(D.n == a.n && D.w == a.w && D.h == a.h, "destination frame count or size");
+    check_frames(D);
     const bool yuv_out = D.format != kFramesBgr;
-    if (!yuv_out) {
-        OPK_CHECK_ARG(D.step >= (size_t)a.w * 3, "row step shorter than the row");
-        a.dst_aligned = (uintptr_t)D.plane[0] % 4 == 0 && D.step % 4 == 0 && D.frame[0] % 4 == 0;
-    } else {
-        OPK_CHECK_ARG(D.format == kFramesNv12 || D.format == kFramesI420, "unknown frame format");
-        OPK_CHECK_ARG(a.w % 2 == 0 && a.h % 2 == 0, "YUV 4:2:0 frames have even width and height");
-        OPK_CHECK_ARG(D.plane[1] && D.plane[2], "NULL plane");
-        OPK_CHECK_ARG(D.cpix == (D.format == kFramesNv12 ? 2 : 1), "chroma sample stride");
-        OPK_CHECK_ARG(D.step >= (size_t)a.w && D.cstep >= (size_t)(a.w / 2) * D.cpix,
-                      "row step shorter than the row");
-        // (NV12's plane[2] is plane[1] + 1: the pairs are stored through plane[1] alone)
-        a.dst_aligned = (uintptr_t)D.plane[0] % 4 == 0 && D.step % 4 == 0 && D.frame[0] % 4 == 0 &&
-                        (uintptr_t)D.plane[1] % 4 == 0 && D.cstep % 4 == 0 && D.frame[1] % 4 == 0 &&
-                        (D.cpix == 2 || ((uintptr_t)D.plane[2] % 4 == 0 && D.frame[2] % 4 == 0));
-    }
+    a.dst_aligned = frames_aligned(D, 4);
     a.dst = D.plane[0];
     a.dst_step = D.step;
     a.dst_frame = D.frame[0];

@@ -25,6 +25,7 @@
 #include "kernels.h"
 #include "yuv_dev.h"
 #include "../common.h"
+#include "../host/frames.h"
 
 namespace opk {
 
@@ -341,15 +342,7 @@ void launch_pyramid(uint8_t* pyr, const PyramidLayout& L, const FrameSource& fs,
     OPK_CHECK_ARG(fs.plane[0] != nullptr, "NULL frames");
     OPK_CHECK_ARG(fs.h <= 65535 && fs.n <= 65535, "more than 65535 rows or frames");
     const bool yuv = fs.format != kFramesBgr;
-    if (yuv) {
-        OPK_CHECK_ARG(fs.format == kFramesNv12 || fs.format == kFramesI420, "unknown frame format");
-        OPK_CHECK_ARG(fs.w % 2 == 0 && fs.h % 2 == 0, "YUV 4:2:0 frames have even width and height");
-        OPK_CHECK_ARG(fs.plane[1] && fs.plane[2], "NULL plane");
-        OPK_CHECK_ARG(fs.step >= (size_t)fs.w && fs.cstep >= (size_t)(fs.w / 2) * fs.cpix,
-                      "row step shorter than the row");
-    } else {
-        OPK_CHECK_ARG(fs.step >= (size_t)fs.w * 3, "row step shorter than the row");
-    }
+    check_frames(fs);
     const dim3 g0((unsigned)((fs.w + 255) / 256), (unsigned)fs.h, (unsigned)fs.n);
     if (yuv) {
         note_launch("track_grey<yuv>");

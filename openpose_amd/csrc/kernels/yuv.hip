@@ -11,6 +11,7 @@
 #include "yuv_dev.h"
 #include "yuv_out_dev.h"
 #include "../common.h"
+#include "../host/frames.h"
 
 namespace opk {
 
@@ -140,7 +141,7 @@ __device__ __forceinline__ uint4 yuv16(const uint4 q[3], unsigned u[8], unsigned
 }
 
 // the 2 x 2 block at even column x of rows s0 / s1 (BGR bytes) -> four luma bytes, one (U, V)
-__device__ __forceinline__ void yuv_block(const YuvOutRow& r0, const YuvOutRow& r1,
+__device__ __forceinline__ void yuv_block(const YuvRowT<uint8_t>& r0, const YuvRowT<uint8_t>& r1,
                                           const uint8_t* s0, const uint8_t* s1, int x)
 {
 #pragma unroll
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(256) void bgr_to_yuv420_kernel(FrameDest dst, Frame
     const int i = blockIdx.x * 256 + threadIdx.x;
     const uint8_t* s0 = fs.plane[0] + (size_t)f * fs.frame[0] + (size_t)y0 * fs.step;
     const uint8_t* s1 = s0 + fs.step;
-    const YuvOutRow r0 = yuv_out_row(dst, f, y0), r1 = yuv_out_row(dst, f, y0 + 1);
+    const YuvRowT<uint8_t> r0 = yuv_row(dst, f, y0), r1 = yuv_row(dst, f, y0 + 1);
     int x = V ? 16 * i : 2 * i;
     if (x >= fs.w) return;
     if (V && x + 16 <= fs.w) {
@@ -296,25 +297,12 @@ __global__ __launch_bounds__(256) void cvmat_to_input_lds_yuv_kernel(
     }
 }
 
+// a YUV source of a launcher here: not BGR, not empty, and check_frames' layout (host/frames.h)
 void check_yuv(const FrameSource& fs)
 {
-    OPK_CHECK_ARG(fs.format == kFramesNv12 || fs.format == kFramesI420, "unknown frame format");
+    OPK_CHECK_ARG(fs.format != kFramesBgr, "unknown frame format");
     OPK_CHECK_ARG(fs.n > 0 && fs.w > 0 && fs.h > 0, "empty frame");
-    OPK_CHECK_ARG(fs.w % 2 == 0 && fs.h % 2 == 0, "YUV 4:2:0 frames have even width and height");
-    OPK_CHECK_ARG(fs.plane[0] && fs.plane[1] && fs.plane[2], "NULL plane");
-    OPK_CHECK_ARG(fs.cpix == (fs.format == kFramesNv12 ? 2 : 1), "chroma sample stride");
-    OPK_CHECK_ARG(fs.step >= (size_t)fs.w && fs.cstep >= (size_t)(fs.w / 2) * fs.cpix,
-                  "row step shorter than the row");
-}
-
-// every 16-byte luma and 16-byte (NV12) / 8-byte (I420) chroma load of a 16-pixel piece is aligned
-bool yuv_aligned(const FrameSource& fs)
-{
-    const bool luma = (uintptr_t)fs.plane[0] % 16 == 0 && fs.step % 16 == 0 && fs.frame[0] % 16 == 0;
-    if (fs.cpix == 2)   // interleaved pairs, read through plane[1] alone
-        return luma && (uintptr_t)fs.plane[1] % 16 == 0 && fs.cstep % 16 == 0 && fs.frame[1] % 16 == 0;
-    return luma && (uintptr_t)fs.plane[1] % 8 == 0 && (uintptr_t)fs.plane[2] % 8 == 0 &&
-           fs.cstep % 8 == 0 && fs.frame[1] % 8 == 0 && fs.frame[2] % 8 == 0;
+    check_frames(fs);
 }
 
 }  // namespace
@@ -325,7 +313,7 @@ void launch_frames_to_bgr(uint8_t* dst, size_t dst_step, const FrameSource& fs, 
     OPK_CHECK_ARG(dst != nullptr, "NULL buffer");
     OPK_CHECK_ARG(dst_step >= (size_t)fs.w * 3, "row step shorter than the row");
     OPK_CHECK_ARG(fs.h / 2 <= 65535 && fs.n <= 65535, "more than 65535 row pairs or frames");
-    const bool vec = yuv_aligned(fs) && (uintptr_t)dst % 16 == 0 && dst_step % 16 == 0;
+    const bool vec = frames_aligned(fs, 16) && (uintptr_t)dst % 16 == 0 && dst_step % 16 == 0;
     const int lanes = vec ? (fs.w + 15) / 16 : fs.w / 2;
     const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)(fs.h / 2), (unsigned)fs.n);
     if (vec) {
@@ -341,28 +329,18 @@ void launch_frames_to_bgr(uint8_t* dst, size_t dst_step, const FrameSource& fs, 
 
 void launch_bgr_to_frames(const FrameDest& dst, const FrameSource& fs, hipStream_t stream)
 {
+    // this site's own checks first and in the order they always had (a BGR destination before an
+    // empty batch, both before a size mismatch); check_frames' layout checks come after them
     OPK_CHECK_ARG(fs.format == kFramesBgr, "the source frames are BGR");
-    OPK_CHECK_ARG(dst.format == kFramesNv12 || dst.format == kFramesI420, "unknown frame format");
+    OPK_CHECK_ARG(dst.format != kFramesBgr, "unknown frame format");
     OPK_CHECK_ARG(fs.n > 0 && fs.w > 0 && fs.h > 0, "empty frame");
     OPK_CHECK_ARG(dst.n == fs.n && dst.w == fs.w && dst.h == fs.h, "frame count or size differs");
-    OPK_CHECK_ARG(fs.w % 2 == 0 && fs.h % 2 == 0, "YUV 4:2:0 frames have even width and height");
-    OPK_CHECK_ARG(fs.plane[0] && dst.plane[0] && dst.plane[1] && dst.plane[2], "NULL plane");
-    OPK_CHECK_ARG(dst.cpix == (dst.format == kFramesNv12 ? 2 : 1), "chroma sample stride");
-    OPK_CHECK_ARG(fs.step >= (size_t)fs.w * 3 && dst.step >= (size_t)fs.w &&
-                      dst.cstep >= (size_t)(fs.w / 2) * dst.cpix,
-                  "row step shorter than the row");
+    OPK_CHECK_ARG(fs.plane[0] != nullptr, "NULL plane");
+    check_frames(dst);
+    check_frames(fs);
     OPK_CHECK_ARG(fs.h / 2 <= 65535 && fs.n <= 65535, "more than 65535 row pairs or frames");
-    // the destination seen as a source has the alignment rules of the 16-pixel pieces
-    FrameSource as{};
-    as.cpix = dst.cpix;
-    as.step = dst.step;
-    as.cstep = dst.cstep;
-    for (int i = 0; i < 3; ++i) {
-        as.plane[i] = dst.plane[i];
-        as.frame[i] = dst.frame[i];
-    }
-    const bool vec = yuv_aligned(as) && (uintptr_t)fs.plane[0] % 16 == 0 && fs.step % 16 == 0 &&
-                     fs.frame[0] % 16 == 0;
+    // both sides move as 16-pixel pieces: 48 source bytes, 16 of luma, 16 (NV12) or 8 + 8 of chroma
+    const bool vec = frames_aligned(dst, 16) && frames_aligned(fs, 16);
     const int lanes = vec ? (fs.w + 15) / 16 : fs.w / 2;
     const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)(fs.h / 2), (unsigned)fs.n);
     if (vec) {
@@ -391,7 +369,7 @@ void launch_cvmat_to_input_yuv(float* dst, const FrameSource& fs, int n, int dh,
     const size_t rows_at = ((size_t)dw * 8 + 64 * ksize * ksize + 15) & ~(size_t)15;
     const size_t lds = rows_at + (size_t)ksize * lds_row;
     if (lds <= 64 * 1024) {
-        const bool a16 = yuv_aligned(fs);
+        const bool a16 = frames_aligned(fs, 16);
 #define OPK_WARP_LDS(K_, A_)                                                                      \
     hipLaunchKernelGGL((cvmat_to_input_lds_yuv_kernel<K_, A_>), grid, dim3(threads), lds, stream, \
                        dst, fs, dh, dw, xt, yt, wtab, normalize, frame_of, tab_stride, lds_row,    \

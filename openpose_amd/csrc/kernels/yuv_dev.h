@@ -54,19 +54,23 @@ __device__ __forceinline__ unsigned yuv_pixel_packed(int Y, const YuvChroma& k)
     return (unsigned)c[0] | (unsigned)c[1] << 8 | (unsigned)c[2] << 16;
 }
 
-// One row of a YUV frame as the warps read it: the luma row and the chroma row that goes with it
-struct YuvRow {
-    const uint8_t* y;
-    const uint8_t* u;
-    const uint8_t* v;
+// One row of a YUV frame: the luma row yy and the chroma row yy >> 1 that goes with it -- where the
+// warps read their taps (B const) and where converted samples go (B writable, yuv_out_dev.h)
+template <class B>
+struct YuvRowT {
+    B* y;
+    B* u;
+    B* v;
     int cpix;
 };
-__device__ __forceinline__ YuvRow yuv_row(const FrameSource& s, int f, int yy)
+using YuvRow = YuvRowT<const uint8_t>;
+template <class B>
+__device__ __forceinline__ YuvRowT<B> yuv_row(const FramesT<B>& s, int f, int yy)
 {
     const size_t c = (size_t)(yy >> 1) * s.cstep;
-    return YuvRow{s.plane[0] + (size_t)f * s.frame[0] + (size_t)yy * s.step,
-                  s.plane[1] + (size_t)f * s.frame[1] + c, s.plane[2] + (size_t)f * s.frame[2] + c,
-                  s.cpix};
+    return YuvRowT<B>{s.plane[0] + (size_t)f * s.frame[0] + (size_t)yy * s.step,
+                      s.plane[1] + (size_t)f * s.frame[1] + c, s.plane[2] + (size_t)f * s.frame[2] + c,
+                      s.cpix};
 }
 // pixel xx of the row as BGR (warp_pixel's tap fetch, warp_dev.h)
 __device__ __forceinline__ void warp_tap(int c[3], const YuvRow& row, int xx)

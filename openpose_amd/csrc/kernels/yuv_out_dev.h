@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "yuv_dev.h"
 
 namespace opk {
 
@@ -39,19 +40,82 @@ __device__ __forceinline__ unsigned bgr_to_v(int b, int g, int r)
     return (unsigned)s >> kYuvOutShift;
 }
 
-// Where the samples of row yy (luma) / chroma row yy >> 1 of frame f go
-struct YuvOutRow {
-    uint8_t* y;
-    uint8_t* u;
-    uint8_t* v;
-    int cpix;
-};
-__device__ __forceinline__ YuvOutRow yuv_out_row(const FrameDest& d, int f, int yy)
+// ---- the store epilogue of the batch render (render.hip) -----------------------------------------
+// A workgroup of 256 lanes holds a 32 x 8 pixel tile at (tx0, ty0), lane tid = 32 * row + column, of
+// which rows x cols pixels lie inside the frame; the lane's pixel (x, y) has the cast bytes
+// (cb, cg, cr).  They become samples here -- every lane its pixel's luma, the lanes at even (x, y)
+// their block's (U, V); w and h are even, so a block lies inside the frame, and the tile, with its
+// top-left.  `stage`: 384 bytes of LDS that nothing else uses any more.
+constexpr int kYuvTileW = 32, kYuvTileH = 8;
+__device__ __forceinline__ void yuv_store_tile(const RenderFramesArgs& a, int f, int x, int y,
+                                               bool inside, unsigned cb, unsigned cg, unsigned cr,
+                                               uint8_t* stage, unsigned tid, int tx0, int ty0,
+                                               int rows, int cols)
 {
-    const size_t c = (size_t)(yy >> 1) * d.cstep;
-    return YuvOutRow{d.plane[0] + (size_t)f * d.frame[0] + (size_t)yy * d.step,
-                     d.plane[1] + (size_t)f * d.frame[1] + c, d.plane[2] + (size_t)f * d.frame[2] + c,
-                     d.cpix};
+    const FrameDest& out = a.out;
+    const unsigned Y = bgr_to_y((int)cb, (int)cg, (int)cr);
+    const bool top = ((x | y) & 1) == 0;
+    const unsigned U = bgr_to_u((int)cb, (int)cg, (int)cr);
+    const unsigned V = bgr_to_v((int)cb, (int)cg, (int)cr);
+    const int cpix = out.cpix;
+    if (!a.dst_aligned) {
+        if (inside) {
+            const YuvRowT<uint8_t> o = yuv_row(out, f, y);
+            o.y[x] = (uint8_t)Y;
+            if (top) {
+                o.u[(x >> 1) * cpix] = (uint8_t)U;
+                o.v[(x >> 1) * cpix] = (uint8_t)V;
+            }
+        }
+        return;
+    }
+    // every plane on 4-byte boundaries (a tile starts at byte 32 * blockIdx.x of its luma and
+    // NV12 chroma rows, 16 * blockIdx.x of its I420 ones): the tile's 8 x 32 luma bytes and
+    // 4 x 32 chroma bytes (NV12: pairs; I420: 16 of U at 256, 16 of V at 320 per row) go through
+    // LDS and leave as 4-byte stores: wave 0 the luma, 8 lanes a row; wave 1 the chroma,
+    // 8 (NV12) or 4 + 4 (I420) lanes a row; what a row has left over as bytes
+    const int lx = tid & (kYuvTileW - 1), ly = tid / kYuvTileW;
+    stage[tid] = (uint8_t)Y;
+    if (top) {
+        if (cpix == 2) {
+            stage[256 + (ly >> 1) * 32 + lx] = (uint8_t)U;
+            stage[256 + (ly >> 1) * 32 + lx + 1] = (uint8_t)V;
+        } else {
+            stage[256 + (ly >> 1) * 16 + (lx >> 1)] = (uint8_t)U;
+            stage[320 + (ly >> 1) * 16 + (lx >> 1)] = (uint8_t)V;
+        }
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6;
+    if (wave > 1) return;
+    uint8_t* d;
+    const uint8_t* s;
+    int left;   // bytes of the row from this lane's first
+    if (wave == 0) {
+        const int row = lane >> 3, o = (lane & 7) * 4;
+        if (row >= rows) return;
+        d = out.plane[0] + (size_t)f * out.frame[0] + (size_t)(ty0 + row) * out.step + tx0 + o;
+        s = stage + row * 32 + o;
+        left = cols - o;
+    } else if (cpix == 2) {
+        const int row = lane >> 3, o = (lane & 7) * 4;
+        if (lane >= 32 || 2 * row >= rows) return;
+        d = out.plane[1] + (size_t)f * out.frame[1] + (size_t)((ty0 >> 1) + row) * out.cstep + tx0 + o;
+        s = stage + 256 + row * 32 + o;
+        left = cols - o;
+    } else {
+        const int p = lane >> 4, row = (lane >> 2) & 3, o = (lane & 3) * 4;   // p: U, V
+        if (lane >= 32 || 2 * row >= rows) return;
+        d = out.plane[1 + p] + (size_t)f * out.frame[1 + p] +
+            (size_t)((ty0 >> 1) + row) * out.cstep + (tx0 >> 1) + o;
+        s = stage + 256 + p * 64 + row * 16 + o;
+        left = (cols >> 1) - o;
+    }
+    if (left >= 4) {
+        *reinterpret_cast<unsigned*>(d) = *reinterpret_cast<const unsigned*>(s);
+    } else {
+        for (int i = 0; i < left; ++i) d[i] = s[i];
+    }
 }
 
 }  // namespace opk
