@@ -337,9 +337,20 @@ int opk_bgr_to_frames(opk_ctx* ctx, const opk_frames_out* dst, const opk_frames*
 /* Kernel-variant switches (no reference counterpart; A/B tests and tuning only): key = one of
  * "CONV3_SMALL", "CONV3_W16", "CONV3_PERSIST", "CONV3_WIDE", "CONV3P_ASMR", "CONV3P_WIDE",
  * "CONV3P_PRIO", "CONV3W", "CONV1_TILE", "CONV1_N64W16", "CONV1_FUSED", "CONV3S_MAX", "LK_WAVE",
- * "TRI_GROUP" (read when a launch is planned);
+ * "TRI_GROUP" and the others named below and at their readers (opk::dev_switch);
  * reset != 0 removes the key (back to the product default).  Process-wide; the environment is
- * never consulted. */
+ * never consulted.
+ * When a net reads them.  A decision switch -- one that chooses which kernel runs a conv, on which
+ * tile, fused with what, on how many compute units: everything the host-side conv planner and the
+ * net's shape planner read, plus "GRID_CUS" and "EPI_MAX" -- is read when a net plans an input
+ * shape (its first forward, prepare or select_output of that shape) and holds for that shape's
+ * plan: later forwards of the shape replay the planned launches.  A new net, opk_net_set_conv,
+ * opk_net_set_precision, opk_net_set_precision_schedule and opk_net_set_small_batch plan again;
+ * setting a decision switch does not, so set it before the net first sees the shape.
+ * opk_net_conv_plan and opk_net_conv_kernels plan afresh on every call.  The flags with which a
+ * launcher picks among instantiations of the planned kernel ("BUFST", "W8_NBX", "CONV3W" = 2,
+ * "CONV3_WIDE", "CONV3P_PRIO", "CONV3P_ASMR", "CONV3P_WIDE", "HEAD_PERSIST", "CONV_IMAGE_WIDE",
+ * "CONV_IMAGE_STAGE") and "LAUNCH_LOG" are read on every forward. */
 int opk_dev_set(const char* key, int value, int reset);
 
 /* ---- Net: replaces op::Net / op::NetCaffe (include/openpose/net/net.hpp:8-18,

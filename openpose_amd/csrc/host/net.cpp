@@ -372,17 +372,20 @@ bool NetHip::fused1_at(int h, int w) const
            border_ == 1 && conv1_fused_supported(h, w, 64, 64);
 }
 
+std::vector<int> NetHip::level_sizes(int size) const
+{
+    std::vector<int> s(nlevels_, size);
+    for (int l = 1; l < nlevels_; ++l) s[l] = (s[l - 1] - 2 + 1) / 2 + 1;   // Caffe ceil sizing for 2x2/2 pooling
+    return s;
+}
+
+// Every decision switch outside conv_plan.cpp is read here (CONV1_FUSED, HEAD_FUSE,
+// HEAD_FUSE_SPLIT, POOL_FUSE), once per planned shape: conv.h, "When a switch is read".
 NetHip::Dispatch NetHip::dispatch(int n, int h, int w, int cus) const
 {
     Dispatch D;
-    D.lh.assign(nlevels_, 0);
-    D.lw.assign(nlevels_, 0);
-    D.lh[0] = h;
-    D.lw[0] = w;
-    for (int l = 1; l < nlevels_; ++l) {   // Caffe ceil sizing for 2x2/2 pooling
-        D.lh[l] = (D.lh[l - 1] - 2 + 1) / 2 + 1;
-        D.lw[l] = (D.lw[l - 1] - 2 + 1) / 2 + 1;
-    }
+    D.lh = level_sizes(h);
+    D.lw = level_sizes(w);
     D.csplit.assign(convs_.size(), 0);
     for (size_t ci = 0; ci < convs_.size(); ++ci) D.csplit[ci] = convs_[ci].precision == kPrecisionSplit;
     D.fused1 = fused1_at(h, w);
@@ -424,6 +427,7 @@ NetHip::Dispatch NetHip::dispatch(int n, int h, int w, int cus) const
     D.poolfused.assign(pools_.size(), 0);
     D.query.assign(convs_.size(), Conv3Query{});
     D.conv.assign(convs_.size(), Conv3Plan{});
+    D.runs.assign(convs_.size(), {});
     for (size_t ci = 0; ci < convs_.size(); ++ci) {
         const ConvPlan& c = convs_[ci];
         if (c.from_image) continue;
@@ -474,6 +478,8 @@ NetHip::Dispatch NetHip::dispatch(int n, int h, int w, int cus) const
             q.xhi = false;
             D.twin[c.in.buf] = 1;
         }
+        const bool in_fused1 = D.fused1 && ((int)ci == fuse1_.a || (int)ci == fuse1_.b);
+        if (!in_fused1 && !(c.head >= 0 && D.headfused[c.head])) D.runs[ci] = conv3_runs(q);
     }
     // a pool follows its input: the split kernel iff the input has a twin, and then writes one
     for (const auto& p : pools_)
@@ -506,28 +512,20 @@ std::vector<std::string> NetHip::conv_kernels(int index, int n, int h, int w, in
         return index == heads_[c.head].a ? std::vector<std::string>{kConvHeadKernel} : std::vector<std::string>{};
     if (c.from_image) return {kConvImageKernel};
     std::vector<std::string> out;
-    Conv3Query q = D.query[index];
-    const int run = conv3_run_frames(q);
-    for (int f0 = 0; f0 < n; f0 += run) {   // as launch_conv3_frames
-        q.frames = std::min(run, n - f0);
-        out.push_back(conv3_plan(q).name);
-    }
+    for (const Conv3Run& r : D.runs[index]) out.push_back(r.plan.name);
     return out;
 }
 
-
 void NetHip::pack(ConvPlan& c)
 {
-    const std::string& name = c.info.name;
-    (void)name;
     const float* w = c.hw.data();
     const float* b = c.hb.data();
     const float* slope = c.hs.empty() ? nullptr : c.hs.data();
     const bool split = c.precision == kPrecisionSplit;
     const int K = c.ksteps * kConvBK;
     const int cin = c.info.cin, k = c.info.k;
-    const bool need_packed = c.from_image;   // conv_image's layout: [cout_pad][64]
-    std::vector<uint16_t> packed(need_packed ? (size_t)c.cout_pad * K : 0, 0);
+    // conv_image's layout: [cout_pad][64]
+    std::vector<uint16_t> packed(c.from_image ? (size_t)c.cout_pad * K : 0, 0);
     auto f2h = [](float v) { _Float16 h = (_Float16)v; return __builtin_bit_cast(uint16_t, h); };
     // split precision: the layer's weights scaled by 2^e, max |w| * 2^e in [2^14, 2^15), so that
     // w_lo = fp16(w' - w_hi) stays a normal fp16 number (ConvArgs::wscale); the kernels multiply
@@ -544,24 +542,16 @@ void NetHip::pack(ConvPlan& c)
     }
     c.wscale = std::ldexp(1.f, -wexp);
     auto wsc = [&](float v) { return std::ldexp(v, wexp); };   // exact (no overflow / underflow here)
-    for (int co = 0; co < c.info.cout && need_packed; ++co) {
-        uint16_t* dst = packed.data() + (size_t)co * K;
-        if (c.from_image) {   // K index (ky*3 + kx)*3 + ci; split: w_lo at K + 32
-            for (int ci = 0; ci < 3; ++ci)
-                for (int ky = 0; ky < 3; ++ky)
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const float wv = wsc(w[(((size_t)co * 3 + ci) * 3 + ky) * 3 + kx]);
-                        const int kk = (ky * 3 + kx) * 3 + ci;
-                        dst[kk] = f2h(wv);
-                        if (split) dst[32 + kk] = f2h(wv - (float)(_Float16)wv);
-                    }
-            continue;
-        }
-        for (int t = 0; t < c.ntaps; ++t) {
-            const int ky = k == 3 ? t / 3 : 0, kx = k == 3 ? t % 3 : 0;
-            for (int ci = 0; ci < cin; ++ci)
-                dst[t * c.cin_pad + ci] = f2h(w[(((size_t)co * cin + ci) * k + ky) * k + kx]);
-        }
+    for (int co = 0; co < c.info.cout && c.from_image; ++co) {
+        uint16_t* dst = packed.data() + (size_t)co * K;   // K index (ky*3 + kx)*3 + ci; split: w_lo at K + 32
+        for (int ci = 0; ci < 3; ++ci)
+            for (int ky = 0; ky < 3; ++ky)
+                for (int kx = 0; kx < 3; ++kx) {
+                    const float wv = wsc(w[(((size_t)co * 3 + ci) * 3 + ky) * 3 + kx]);
+                    const int kk = (ky * 3 + kx) * 3 + ci;
+                    dst[kk] = f2h(wv);
+                    if (split) dst[32 + kk] = f2h(wv - (float)(_Float16)wv);
+                }
     }
     // conv3.hip layout: [cout_pad/BN][cin_pad/32][ky][kx][n BN][ci 32]; split precision: two
     // blocks of chunks, [cout_pad/BN][2][cin_pad/32]..., holding w_hi and w_lo -- the K loop's
@@ -652,13 +642,7 @@ bool NetHip::ready() const
 
 double NetHip::flops_per_frame(int h, int w) const
 {
-    std::vector<int> H(nlevels_), W(nlevels_);
-    H[0] = h;
-    W[0] = w;
-    for (int l = 1; l < nlevels_; ++l) {
-        H[l] = (H[l - 1] - 2 + 1) / 2 + 1;
-        W[l] = (W[l - 1] - 2 + 1) / 2 + 1;
-    }
+    const std::vector<int> H = level_sizes(h), W = level_sizes(w);
     double f = 0;
     for (const auto& c : convs_)
         f += 2.0 * H[c.level] * W[c.level] * c.info.cout * c.info.cin * c.info.k * c.info.k;
@@ -680,18 +664,16 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
         if (cur_ == shapes_.front().get()) cur_ = nullptr;
         shapes_.erase(shapes_.begin());
     }
-    shapes_.push_back(std::make_unique<ShapePlan>());
-    ShapePlan& S = *shapes_.back();
-    // what runs (host only), then the memory and the pointers
+    auto sp = std::make_unique<ShapePlan>();   // (kept only once complete: planning may throw)
+    ShapePlan& S = *sp;
+    // what runs (host only), then the memory and the pointers, then the launch list
     // GRID_CUS (opk_dev_set, dev): persistent grids of fewer CUs, e.g. two pipelines on
-    // concurrent streams sharing the chip
-    const int cus = std::min(cus_, std::max(1, dev_switch("GRID_CUS", cus_)));
-    static_cast<Dispatch&>(S) = dispatch(n, h, w, cus);
+    // concurrent streams sharing the chip.  Read here and nowhere else.
+    S.cus = std::min(cus_, std::max(1, dev_switch("GRID_CUS", cus_)));
+    static_cast<Dispatch&>(S) = dispatch(n, h, w, S.cus);
     S.n = n;
     S.h = h;
     S.w = w;
-    const std::vector<int>& lh_ = S.lh;
-    const std::vector<int>& lw_ = S.lw;
     std::vector<uint16_t*>& ptr = S.base;
     ptr.assign(bufs_.size(), nullptr);
     S.base_lo.assign(bufs_.size(), nullptr);
@@ -713,8 +695,8 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
         // zeroed guards: the kernels read up to W+3 positions before the first frame and up to
         // kConvGuardTail positions after the last one (conv.h)
         const int L = bufs_[i].level, B = border_;
-        const size_t head = (size_t)B * (lw_[L] + 2 * B) + B + 64;
-        const size_t pos = head + (size_t)n * (lh_[L] + 2 * B) * (lw_[L] + 2 * B) + kConvGuardTail;
+        const size_t head = (size_t)B * (S.lw[L] + 2 * B) + B + 64;
+        const size_t pos = head + (size_t)n * (S.lh[L] + 2 * B) * (S.lw[L] + 2 * B) + kConvGuardTail;
         const size_t bytes = pos * bufs_[i].cs * 2;
         OPK_CHECK_ARG(pos * bufs_[i].cs < (size_t)1 << 31, "activation buffer exceeds 2^31 elements");
         uint16_t* raw = static_cast<uint16_t*>(S.mem.back()->get(bytes));
@@ -727,15 +709,28 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
             S.base_lo[i] = rl + head * bufs_[i].cs;
         }
     }
-    const size_t out_bytes = (size_t)n * out_c_ * lh_[out_level_] * lw_[out_level_] * 4;
+    const size_t out_bytes = (size_t)n * out_c_ * S.lh[out_level_] * S.lw[out_level_] * 4;
     S.out32 = static_cast<float*>(S.out_mem.get(out_bytes));
-    void* sink = sink_.get(kConv3SinkBytes);
-    S.args.assign(convs_.size(), ConvArgs{});
-    S.use3.assign(convs_.size(), 0);
-    for (size_t ci = 0; ci < convs_.size(); ++ci) {
+    S.launches = launch_list(S, sink_.get(kConv3SinkBytes));
+    shapes_.push_back(std::move(sp));
+    return &S;
+}
+
+// A forward over the planned shape as a list of kernel launches, in order, every argument final
+// but the input pointer and the fp32 output buffer (forward_steps()): the steps of the graph under
+// S's decisions -- fusions, pooled epilogues, frame runs -- over S's buffers.  EPI_MAX is read here
+// and nowhere else.
+std::vector<NetHip::Launch> NetHip::launch_list(const ShapePlan& S, void* sink) const
+{
+    const int n = S.n, B = border_;
+    const std::vector<uint16_t*>& ptr = S.base;
+    // EPI_MAX=0 (opk_dev_set, dev A/B): the select activation in every epilogue
+    const bool epi_max = dev_switch("EPI_MAX", 1) != 0;
+    // a conv's arguments over the whole batch (out32: the start of the output buffer, set per forward)
+    auto conv_args = [&](int ci) {
         const ConvPlan& c = convs_[ci];
-        ConvArgs& a = S.args[ci];
-        const int H = lh_[c.level], W = lw_[c.level], Wp = W + 2 * border_;
+        ConvArgs a{};
+        const int H = S.lh[c.level], W = S.lw[c.level], Wp = W + 2 * B;
         a.in = ptr[c.in.buf];
         a.in_cs = bufs_[c.in.buf].cs;
         a.in_coff = c.in.coff;
@@ -745,23 +740,18 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
             for (int t = 0; t < 9; ++t) a.tapoff[t] = (t / 3) * Wp + (t % 3);
         else if (a.ntaps == 1)
             a.tapoff[0] = Wp + 1;
-        a.border = border_;
+        a.border = B;
         a.ksteps = c.ksteps;
-        const bool use3 = !c.from_image;
-        S.use3[ci] = use3;
-        OPK_CHECK_ARG(use3 || c.w.ptr != nullptr, c.info.name + ": weights not set");
-        if (use3) {   // (the launchers plan again from these arguments and hold sw / nstrips against it)
-            a.sw = S.conv[ci].sw;
-            a.nstrips = S.conv[ci].nstrips;
-            a.small = S.conv[ci].family == Conv3Family::conv3s;
+        OPK_CHECK_ARG(!c.from_image || c.w.ptr != nullptr, c.info.name + ": weights not set");
+        if (!c.from_image) {
             a.sink = sink;
-            a.cus = cus;
+            a.cus = S.cus;
         }
-        a.w = static_cast<const uint16_t*>(use3 ? c.w3.ptr : c.w.ptr);
+        a.w = static_cast<const uint16_t*>(c.from_image ? c.w.ptr : c.w3.ptr);
         a.bias = static_cast<const float*>(c.bias.ptr);
         a.slope = static_cast<const float*>(c.slope.ptr);
         a.act = c.info.act;
-        a.actmax = dev_switch("EPI_MAX", 1) != 0;   // and the conv's slopes (at launch: set_conv may follow)
+        a.actmax = epi_max && c.slope01;
         a.frames = n;
         a.H = H;
         a.W = W;
@@ -777,10 +767,10 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
         }
         a.split = S.csplit[ci] ? 1 : 0;
         a.wscale = S.csplit[ci] ? c.wscale : 1.f;
-        // (no lo pointer: the hi-only plan, as conv3_query reads it)
-        a.in_lo = S.csplit[ci] && use3 && !S.query[ci].xhi ? S.base_lo[c.in.buf] : nullptr;
+        // (no lo pointer: the hi-only plan)
+        a.in_lo = S.csplit[ci] && !c.from_image && !S.query[ci].xhi ? S.base_lo[c.in.buf] : nullptr;
         for (size_t q = 0; q < pools_.size(); ++q)
-            if (S.poolfused[q] && pool_conv_[q] == (int)ci) {   // the pooled image instead
+            if (S.poolfused[q] && pool_conv_[q] == ci) {   // the pooled image instead
                 a.pool = 1;
                 a.ndst = 1;
                 a.dst[0] = ptr[pools_[q].out_buf];
@@ -794,8 +784,126 @@ NetHip::ShapePlan* NetHip::shape_plan(int n, int h, int w, hipStream_t zero_stre
             a.out32_c = out_c_;
             a.out32_coff = c.out32_coff;
         }
+        return a;
+    };
+    std::vector<Launch> list;
+    auto add = [&](Launch::Kind kind, const std::string& layer) -> Launch& {
+        list.emplace_back();
+        list.back().kind = kind;
+        list.back().layer = layer;
+        return list.back();
+    };
+    size_t first = 0;
+    if (S.fused1) {
+        const ConvPlan& a = convs_[fuse1_.a];
+        const ConvPlan& b = convs_[fuse1_.b];
+        const PoolPlan& p = pools_[fuse1_.p];
+        Conv1FusedArgs& fa = add(Launch::kConv1Fused, a.info.name + "+" + b.info.name + "+pool").fused1;
+        fa.frames = n;
+        fa.H = S.h;
+        fa.W = S.w;
+        fa.w1 = static_cast<const uint16_t*>(a.w.ptr);
+        fa.b1 = static_cast<const float*>(a.bias.ptr);
+        fa.s1 = static_cast<const float*>(a.slope.ptr);
+        fa.act1 = a.info.act;
+        fa.w2 = static_cast<const uint16_t*>(b.w3.ptr);
+        fa.b2 = static_cast<const float*>(b.bias.ptr);
+        fa.s2 = static_cast<const float*>(b.slope.ptr);
+        fa.act2 = b.info.act;
+        fa.out = ptr[p.out_buf];
+        fa.out_cs = bufs_[p.out_buf].cs;
+        fa.out_coff = 0;
+        fa.OH = S.lh[1];
+        fa.OW = S.lw[1];
+        fa.actmax = a.slope01 && b.slope01 && epi_max;
+        first = 3;
     }
-    return &S;
+    for (size_t si = first; si < steps_.size(); ++si) {
+        const Step& s = steps_[si];
+        if (!s.conv) {
+            if (S.poolfused[s.idx]) continue;   // runs in its conv's epilogue
+            const PoolPlan& p = pools_[s.idx];
+            const int lv = p.level_in;
+            // a pool follows its input: the split kernel iff the input has a twin
+            const bool split = S.twin[p.in_buf];
+            add(Launch::kPool, "pool").pool =
+                PoolArgs{ptr[p.out_buf], split ? S.base_lo[p.out_buf] : nullptr, ptr[p.in_buf],
+                         split ? S.base_lo[p.in_buf] : nullptr, n, S.lh[lv], S.lw[lv],
+                         bufs_[p.in_buf].cs, S.lh[lv + 1], S.lw[lv + 1]};
+            continue;
+        }
+        const ConvPlan& c = convs_[s.idx];
+        const ConvArgs a = conv_args(s.idx);
+        if (c.head >= 0 && S.headfused[c.head] && heads_[c.head].step == (int)si) {
+            const FuseHead& fh = heads_[c.head];
+            const ConvPlan& cb = convs_[fh.b];
+            const ConvArgs b = conv_args(fh.b);
+            Launch& L = add(Launch::kConvHead, c.info.name + "+" + cb.info.name);
+            HeadArgs& h = L.head;
+            h.in = a.in;
+            h.in_cs = a.in_cs;
+            h.in_coff = a.in_coff;
+            h.cin_pad = a.cin_pad;
+            h.w6 = static_cast<const uint16_t*>(c.wh.ptr);
+            h.b6 = a.bias;
+            h.s6 = a.slope;
+            h.act6 = a.act;
+            h.actmax = a.actmax;
+            h.w7 = static_cast<const uint16_t*>(cb.wh.ptr);
+            h.b7 = b.bias;
+            h.n1 = c.info.cout;
+            h.n2 = cb.info.cout;
+            h.frames = n;
+            h.H = a.H;
+            h.W = a.W;
+            h.ndst = b.ndst;
+            for (int d = 0; d < b.ndst; ++d) {
+                h.dst[d] = b.dst[d];
+                h.dst_cs[d] = b.dst_cs[d];
+                h.dst_coff[d] = b.dst_coff[d];
+            }
+            if (b.out32) L.out32 = 0;
+            h.out32_c = b.out32_c;
+            h.out32_coff = b.out32_coff;
+            h.cus = S.cus;   // the persistent grid (launch_conv_head)
+            if (S.csplit[s.idx]) {
+                h.split = 1;
+                h.in_lo = a.in_lo;
+                for (int d = 0; d < b.ndst; ++d) h.dst_lo[d] = b.dst_lo[d];
+                h.wscale6 = a.wscale;
+                h.wscale7 = b.wscale;
+            }
+            ++si;   // Mconv7 runs inside
+            continue;
+        }
+        const std::string layer = c.info.name + (a.pool ? "+pool" : "");
+        if (c.from_image) {
+            add(Launch::kConvImage, layer).conv = a;
+            continue;
+        }
+        // One launch per run of whole frames (conv3_runs), its pointers moved to the run's first
+        // frame: the positions just before and after a run are frame borders, zero like the
+        // guards of a whole-batch launch.  (Several runs: the full-resolution layers of a large
+        // batch, which run unfused only in split precision.)
+        const size_t frame_pos = (size_t)(a.H + 2 * B) * (a.W + 2 * B);   // padded image positions
+        // a pooled destination (conv3w8 POOL epilogue) holds the pooled padded image per frame
+        const size_t dst_pos = a.pool ? (size_t)(a.H / 2 + 2 * B) * (a.W / 2 + 2 * B) : frame_pos;
+        for (const Conv3Run& r : S.runs[s.idx]) {
+            Launch& R = add(Launch::kConv3, layer);
+            R.plan = r.plan;
+            ConvArgs& b = R.conv = a;
+            b.frames = r.frames;
+            b.M = r.frames * a.H * (a.W + 2 * B);
+            b.in = a.in + r.f0 * frame_pos * a.in_cs;
+            if (a.in_lo) b.in_lo = a.in_lo + r.f0 * frame_pos * a.in_cs;
+            for (int d = 0; d < a.ndst; ++d) {
+                b.dst[d] = a.dst[d] + r.f0 * dst_pos * a.dst_cs[d];
+                if (a.dst_lo[d]) b.dst_lo[d] = a.dst_lo[d] + r.f0 * dst_pos * a.dst_cs[d];
+            }
+            if (a.out32) R.out32 = (long)r.f0 * a.out32_c * a.H * a.W;
+        }
+    }
+    return list;
 }
 
 void NetHip::forward(const float* input, int n, int h, int w)
@@ -855,7 +963,7 @@ void NetHip::forward_on(const float* input, int n, int h, int w, hipStream_t st,
     for (const auto& r : readers_)   // post-processings still reading this output buffer
         if (r.first == S.out()) OPK_HIP(hipStreamWaitEvent(st, r.second, 0));
     if (timed) timer_.begin(st);
-    forward_launches(S, input, n, h, w, st);
+    forward_launches(S, input, st);
     if (timed) timer_.end(st);
 }
 
@@ -926,7 +1034,7 @@ void NetHip::read_planes(const std::string& name, int f0, int nf, float* hi, flo
             }
 }
 
-void NetHip::forward_launches(ShapePlan& S, const float* input, int n, int h, int w, hipStream_t st)
+void NetHip::forward_launches(ShapePlan& S, const float* input, hipStream_t st)
 {
     const bool logging = dev_switch("LAUNCH_LOG", 0) != 0;
     // the log attached before (opk_launch_log_begin) comes back after this forward
@@ -940,156 +1048,42 @@ void NetHip::forward_launches(ShapePlan& S, const float* input, int n, int h, in
         LaunchLog* before;
         ~Detach() { if (on) attach_launch_log(before); }
     } detach{logging, before};
-    forward_steps(S, input, n, h, w, st);
+    forward_steps(S, input, st);
 }
 
-// conv3 over the frames of a batch in as few launches as its 24-bit position arithmetic allows
-// (the full-resolution layers of a large batch run unfused only in split precision): each launch
-// takes a run of whole frames, its pointers moved to the run's first frame -- the positions just
-// before and after a run are frame borders, zero like the guards of a whole-batch launch.
-//
-// Runs are sized evenly (conv3_run_frames: ceil(frames / runs) frames each), and each run takes the
-// plan of ITS frame count: the planner's sw / nstrips were chosen for the whole batch, and a run
-// with fewer tiles may fall into another tile branch (another halo, so another strip count) --
-// launch_conv3 requires the geometry of its own frame count.
-static void launch_conv3_frames(const ConvArgs& a, hipStream_t st)
-{
-    const int B = a.border > 0 ? a.border : 1;
-    Conv3Query q = conv3_query(a);
-    const int run = conv3_run_frames(q);
-    if (run == a.frames) {
-        launch_conv3(a, st);
-        return;
-    }
-    const size_t frame_pos = (size_t)(a.H + 2 * B) * (a.W + 2 * B);   // padded image positions
-    // a pooled destination (conv3w8 POOL epilogue) holds the pooled padded image per frame
-    const size_t dst_pos = a.pool ? (size_t)(a.H / 2 + 2 * B) * (a.W / 2 + 2 * B) : frame_pos;
-    for (int f0 = 0; f0 < a.frames; f0 += run) {
-        ConvArgs b = a;
-        b.frames = std::min(run, a.frames - f0);
-        q.frames = b.frames;
-        const Conv3Plan pb = conv3_plan(q);
-        b.sw = pb.sw;
-        b.nstrips = pb.nstrips;
-        b.M = b.frames * a.H * (a.W + 2 * B);
-        b.in = a.in + f0 * frame_pos * a.in_cs;
-        if (a.in_lo) b.in_lo = a.in_lo + f0 * frame_pos * a.in_cs;
-        for (int d = 0; d < a.ndst; ++d) {
-            b.dst[d] = a.dst[d] + f0 * dst_pos * a.dst_cs[d];
-            if (a.dst_lo[d]) b.dst_lo[d] = a.dst_lo[d] + f0 * dst_pos * a.dst_cs[d];
-        }
-        if (a.out32) b.out32 = a.out32 + (size_t)f0 * a.out32_c * a.H * a.W;
-        launch_conv3(b, st);
-    }
-}
-
-void NetHip::forward_steps(ShapePlan& S, const float* input, int n, int h, int w, hipStream_t st)
+// Replays the shape's launch list.  Nothing is decided here and no decision switch is read: only
+// the input pointer and this forward's output buffer (select_output) are filled in.
+void NetHip::forward_steps(ShapePlan& S, const float* input, hipStream_t st)
 {
     LaunchLog* log = launch_log();
-    float* const out32 = S.out();   // this forward's output buffer (select_output)
-    const std::vector<uint16_t*>& ptr = S.base;
-    const std::vector<int>& lh_ = S.lh;
-    const std::vector<int>& lw_ = S.lw;
-    size_t first = 0;
-    if (S.fused1) {
-        const ConvPlan& a = convs_[fuse1_.a];
-        const ConvPlan& b = convs_[fuse1_.b];
-        const PoolPlan& p = pools_[fuse1_.p];
-        Conv1FusedArgs fa{};
-        fa.img = input;
-        fa.frames = n;
-        fa.H = h;
-        fa.W = w;
-        fa.w1 = static_cast<const uint16_t*>(a.w.ptr);
-        fa.b1 = static_cast<const float*>(a.bias.ptr);
-        fa.s1 = static_cast<const float*>(a.slope.ptr);
-        fa.act1 = a.info.act;
-        fa.w2 = static_cast<const uint16_t*>(b.w3.ptr);
-        fa.b2 = static_cast<const float*>(b.bias.ptr);
-        fa.s2 = static_cast<const float*>(b.slope.ptr);
-        fa.act2 = b.info.act;
-        fa.out = ptr[p.out_buf];
-        fa.out_cs = bufs_[p.out_buf].cs;
-        fa.out_coff = 0;
-        fa.OH = lh_[1];
-        fa.OW = lw_[1];
-        fa.actmax = a.slope01 && b.slope01 && dev_switch("EPI_MAX", 1) != 0;
-        if (log) log->layer = a.info.name + "+" + b.info.name + "+pool";
-        launch_conv1_fused(fa, std::min(cus_, std::max(1, dev_switch("GRID_CUS", cus_))), st);
-        first = 3;
-    }
-    for (size_t si = first; si < steps_.size(); ++si) {
-        const Step& s = steps_[si];
-        if (s.conv) {
-            const ConvPlan& c = convs_[s.idx];
-            const ConvArgs& a = S.args[s.idx];
-            if (c.head >= 0 && S.headfused[c.head] && heads_[c.head].step == (int)si) {
-                const FuseHead& fh = heads_[c.head];
-                const ConvPlan& cb = convs_[fh.b];
-                const ConvArgs& b = S.args[fh.b];
-                HeadArgs h{};
-                h.in = a.in;
-                h.in_cs = a.in_cs;
-                h.in_coff = a.in_coff;
-                h.cin_pad = a.cin_pad;
-                h.w6 = static_cast<const uint16_t*>(c.wh.ptr);
-                h.b6 = a.bias;
-                h.s6 = a.slope;
-                h.act6 = a.act;
-                h.actmax = a.actmax && c.slope01;
-                h.w7 = static_cast<const uint16_t*>(cb.wh.ptr);
-                h.b7 = b.bias;
-                h.n1 = c.info.cout;
-                h.n2 = cb.info.cout;
-                h.frames = n;
-                h.H = a.H;
-                h.W = a.W;
-                h.ndst = b.ndst;
-                for (int d = 0; d < b.ndst; ++d) {
-                    h.dst[d] = b.dst[d];
-                    h.dst_cs[d] = b.dst_cs[d];
-                    h.dst_coff[d] = b.dst_coff[d];
-                }
-                h.out32 = b.out32 ? out32 : nullptr;
-                h.out32_c = b.out32_c;
-                h.out32_coff = b.out32_coff;
-                // persistent grid (HEAD_PERSIST=0: one workgroup per tile, dev A/B)
-                h.cus = dev_switch("HEAD_PERSIST", 1) != 0 ? a.cus : 0;
-                if (S.csplit[s.idx]) {
-                    h.split = 1;
-                    h.in_lo = a.in_lo;
-                    for (int d = 0; d < b.ndst; ++d) h.dst_lo[d] = b.dst_lo[d];
-                    h.wscale6 = a.wscale;
-                    h.wscale7 = b.wscale;
-                }
-                if (log) log->layer = c.info.name + "+" + cb.info.name;
-                launch_conv_head(h, st);
-                ++si;   // Mconv7 ran inside
-                continue;
-            }
-            if (log) log->layer = c.info.name + (a.pool ? "+pool" : "");
-            if (c.from_image) {
-                ConvArgs ai = a;
-                if (ai.out32) ai.out32 = out32;
-                launch_conv_image(ai, input, st);
-            } else {
-                ConvArgs a3 = a;
-                a3.actmax = a.actmax && c.slope01;
-                if (a3.out32) a3.out32 = out32;
-                launch_conv3_frames(a3, st);
-            }
-        } else {
-            if (S.poolfused[s.idx]) continue;   // ran in its conv's epilogue
-            const PoolPlan& p = pools_[s.idx];
-            const int L = p.level_in;
-            if (log) log->layer = "pool";
-            if (S.twin[p.in_buf])
-                launch_maxpool2_split(ptr[p.out_buf], S.base_lo[p.out_buf], ptr[p.in_buf],
-                                      S.base_lo[p.in_buf], n, lh_[L], lw_[L], bufs_[p.in_buf].cs,
-                                      lh_[L + 1], lw_[L + 1], st, border_);
+    float* const out32 = S.out();
+    for (Launch& L : S.launches) {
+        if (log) log->layer = L.layer;
+        switch (L.kind) {
+        case Launch::kConv1Fused:
+            L.fused1.img = input;
+            launch_conv1_fused(L.fused1, S.cus, st);
+            break;
+        case Launch::kConvHead:
+            if (L.out32 >= 0) L.head.out32 = out32 + L.out32;
+            launch_conv_head(L.head, st);
+            break;
+        case Launch::kConvImage:
+            launch_conv_image(L.conv, input, st);
+            break;
+        case Launch::kConv3:
+            if (L.out32 >= 0) L.conv.out32 = out32 + L.out32;
+            launch_conv3(L.conv, L.plan, st);
+            break;
+        case Launch::kPool: {
+            const PoolArgs& p = L.pool;
+            if (p.in_lo)
+                launch_maxpool2_split(p.out, p.out_lo, p.in, p.in_lo, p.frames, p.H, p.W, p.C, p.OH, p.OW,
+                                      st, border_);
             else
-                launch_maxpool2(ptr[p.out_buf], ptr[p.in_buf], n, lh_[L], lw_[L],
-                                bufs_[p.in_buf].cs, lh_[L + 1], lw_[L + 1], st, border_);
+                launch_maxpool2(p.out, p.in, p.frames, p.H, p.W, p.C, p.OH, p.OW, st, border_);
+            break;
+        }
         }
     }
 }

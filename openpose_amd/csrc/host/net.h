@@ -160,12 +160,37 @@ private:
         std::vector<char> poolfused;   // per pool: run inside its conv's epilogue (conv3w8 POOL)
         std::vector<Conv3Query> query; // per conv (not the image conv): the whole batch's query
         std::vector<Conv3Plan> conv;   // ... and its plan
+        // per conv that runs a halo kernel of its own (not the image conv, not inside
+        // conv1_fused_kernel / conv_head_kernel): its launches (conv3_runs)
+        std::vector<std::vector<Conv3Run>> runs;
     };
     Dispatch dispatch(int n, int h, int w, int cus) const;
+    std::vector<int> level_sizes(int size) const;   // a side of every pooling level
+
+    struct PoolArgs {
+        uint16_t *out, *out_lo;        // (lo twins: the split pool)
+        const uint16_t *in, *in_lo;
+        int frames, H, W, C, OH, OW;
+    };
+    // One kernel launch of a forward, its arguments finished when the shape is planned
+    // (launch_list()); a forward replays the list and fills in only the input pointer and the
+    // fp32 output buffer it writes (ShapePlan::out()).
+    struct Launch {
+        enum Kind { kConv1Fused, kConvHead, kConvImage, kConv3, kPool } kind;
+        std::string layer;             // launch-log label
+        Conv1FusedArgs fused1{};       // kConv1Fused
+        HeadArgs head{};               // kConvHead
+        ConvArgs conv{};               // kConvImage; kConv3: pointers at the run's first frame
+        Conv3Plan plan{};              // kConv3: the run's plan
+        PoolArgs pool{};               // kPool
+        long out32 = -1;               // kConvHead / kConv3 writing the net output: the floats
+                                       // between the output buffer's start and the run's first frame
+    };
 
     // shape-dependent state of one input shape
     struct ShapePlan : Dispatch {
         int n = 0, h = 0, w = 0;
+        int cus = 0;                   // compute units planned for (GRID_CUS)
         std::vector<std::unique_ptr<DevBuf>> mem;
         std::vector<uint16_t*> base;   // first position of each buffer (past its head guard)
         std::vector<std::unique_ptr<DevBuf>> mem_lo;
@@ -175,13 +200,13 @@ private:
         float* out32_alt = nullptr;    // the second output buffer (select_output)
         bool alt = false;              // forwards write out32_alt
         float* out() const { return alt ? out32_alt : out32; }
-        std::vector<ConvArgs> args;    // per conv
-        std::vector<char> use3;        // per conv: launch conv3
+        std::vector<Launch> launches;  // a forward, in launch order
     };
 
     void plan(const std::vector<LayerDesc>& layers);
-    void forward_launches(ShapePlan& S, const float* input, int n, int h, int w, hipStream_t st);
-    void forward_steps(ShapePlan& S, const float* input, int n, int h, int w, hipStream_t st);
+    std::vector<Launch> launch_list(const ShapePlan& S, void* sink) const;
+    void forward_launches(ShapePlan& S, const float* input, hipStream_t st);
+    void forward_steps(ShapePlan& S, const float* input, hipStream_t st);
     ShapePlan* shape_plan(int n, int h, int w, hipStream_t zero_stream = nullptr);
 
     Context* ctx_;

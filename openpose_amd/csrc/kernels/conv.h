@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 namespace opk {
 
@@ -34,12 +35,13 @@ struct ConvArgs {
     int dst_cs[kConvMaxDst], dst_coff[kConvMaxDst];
     float* out32;         // optional NCHW fp32 [frames][out32_c][H][W]
     int out32_c, out32_coff;
-    int sw, nstrips;      // conv3 only: strip width and count (conv3_plan)
-    float rcp[3];         // conv3 only, set by launch_conv3: 1/((H+2)(sw+2)), 1/(sw+2), 1/nstrips
+    int sw, nstrips;      // conv3 only: strip width and count (set from the plan: conv3_planned_args)
+    float rcp[3];         // conv3 only, set from the plan: 1/((H+2)(sw+2)), 1/(sw+2), 1/nstrips
     int wide;             // conv3 only, set by launch_conv3: 16-byte epilogue stores allowed (CONV3_WIDE)
     int prio;             // conv3 persistent: s_setprio(1) around each unit's MFMAs (CONV3P_PRIO)
     void* sink;           // conv3 persistent variant: >= kConv3SinkBytes of scratch (masked stores)
-    int cus;              // conv3 persistent variant: compute units (grid size); 0 disables it
+    int cus;              // compute units the conv was planned for.  No kernel and no launcher reads
+                          // it back (the grid is the plan's); conv3_query, for the probe tools, does
     int border;           // zero border of the padded images (conv3 / conv_image; 0 means 1)
     int actmax;           // conv3w / conv3w8: every negative-side multiplier (1 none, 0 ReLU, the
                           // PReLU slopes) lies in [0, 1], so t > 0 ? t : t*m == max(t, t*m) for
@@ -68,7 +70,8 @@ struct ConvArgs {
     const uint16_t* in_lo;
     uint16_t* dst_lo[kConvMaxDst];
     float wscale;
-    int small;            // planned on conv3s tiles (NetHip small-batch mode): sw / nstrips are the conv3s plan's
+    int small;            // small-batch tiles asked for.  No kernel and no launcher reads it back (the
+                          // launchers take a Conv3Plan); conv3_query, for the probe tools, does
     int pbn;              // conv3s only, set by conv3_planned_args: the n-block of the weight packing
 };
 // the product of a split virtual chunk (3c + k) that reads w_lo: k = 0 (the order above; dev A/B
@@ -90,8 +93,9 @@ constexpr size_t kConv3SinkBytes = (size_t)1024 * 1024 * 16;   // 1024 lanes x 1
 constexpr int kConvPersistBM = 512, kConvPersistHR = 688;
 
 // ---- conv_plan.cpp: the one decider of which kernel runs a conv, on which tile, strips and grid --
-// Plain host code (no HIP calls): NetHip's planner, its frame runs, the launchers below,
-// opk_net_conv_plan and opk_net_conv_kernels all ask conv3_plan and nothing else decides.
+// Plain host code (no HIP calls): NetHip's planner (once per input shape: its launch list,
+// opk_net_conv_plan and opk_net_conv_kernels read that one answer) and the probe tools ask
+// conv3_plan / conv3_runs and nothing else decides; the launchers below take the plan they are given.
 //
 // Positions are decoded by float-reciprocal division in the kernels (Strips::map), exact below
 // 2^24: a launch's last position (tile and halo overhang included) must fit
@@ -145,7 +149,7 @@ struct Conv3Plan {
     // M = frames * H * (W + 2 border) positions times n-blocks (the grid also covers the border
     // rows and the strips' shared columns: a few per cent more; persistent grids stop at cus)
     long workgroups;
-    bool fits;                    // conv_positions_fit: false -> fewer frames per launch (conv3_run_frames)
+    bool fits;                    // conv_positions_fit: false -> fewer frames per launch (conv3_runs)
     float rcp[3];                 // 1/((H + 2B) VW), 1/VW, 1/nstrips (ConvArgs::rcp)
     // launch-log name: the whole instantiation for conv3_kernel / conv3s_kernel (hi-only:
     // "...,split,xhi>"), up to the parameters the plan fixes for the persistent kernels
@@ -154,17 +158,32 @@ struct Conv3Plan {
     // conv3_kernel, conv3w8x_kernel<...> of conv3w8_kernel (XHI = true)
     char name[64];
 };
-// Every decision switch is read here (opk_dev_set; per call, so tests compare variants in one
-// process): CONV3_SMALL, CONV3_W16, CONV3_PERSIST, CONV1_TILE, CONV1_N64W16, CONV3W8_64, SPLIT_W8,
-// CONV3W8N, CONV3W (0 / not), CONV3W8, CONV3S_MAX, CONV7S_BIG, SPLIT_XHI, SPLIT_XHI_W8.  Throws for sizes no kernel covers
+// Every decision switch of the halo kernels is read here (opk_dev_set; per call, so tests compare
+// variants in one process): CONV3_SMALL, CONV3_W16, CONV3_PERSIST, CONV1_TILE, CONV1_N64W16,
+// CONV3W8_64, SPLIT_W8, CONV3W8N, CONV3W (0 / not), CONV3W8, CONV3S_MAX, CONV7S_BIG, SPLIT_XHI,
+// SPLIT_XHI_W8.
+// When a switch is read.  A *decision* switch -- those above, the ones NetHip::dispatch reads
+// (CONV1_FUSED, HEAD_FUSE, HEAD_FUSE_SPLIT, POOL_FUSE), GRID_CUS and EPI_MAX -- is read when NetHip
+// plans an input shape and holds for that shape's plan: forwards replay the planned launches and
+// ask nothing again.  A new net, set_conv, set_precision* and set_small_batch re-plan; flipping a
+// decision switch on a net that already holds a plan for a shape leaves that shape's forwards as
+// they were.  The launchers' own instantiation flags (BUFST, W8_NBX, CONV3W=2, CONV3_WIDE,
+// CONV3P_PRIO, CONV3P_ASMR, CONV3P_WIDE, HEAD_PERSIST, CONV_IMAGE_WIDE, CONV_IMAGE_STAGE) and
+// LAUNCH_LOG are read per forward.  Throws for sizes no kernel covers
 // and for a plan whose tile is not on the list of instantiations (conv_tiles.h): "no instantiation of <name>".
 // only: a probe tool's choice among the persistent kernels of a conv that supports it (-1: the
 // product rule); plan.family differs from it when the conv does not.
 Conv3Plan conv3_plan(const Conv3Query& q, int only = -1);
-// frames per launch: q.frames when the plan fits a launch's position range, else the even run
-// size (ceil(frames / runs), fewest runs) at which every run -- planned for its own frame count --
-// fits
-int conv3_run_frames(const Conv3Query& q);
+// The launches of a conv over q.frames frames: one run of whole frames per launch, as few as the
+// kernels' position range allows.  One run when the whole batch's plan fits; else the fewest even
+// runs (ceil(frames / runs) frames each, the last one the rest) whose every run fits.  Each run
+// carries the plan of ITS frame count: a run with fewer tiles may fall into another tile branch
+// (another halo, so another strip count) than the whole batch.  Nothing else walks runs.
+struct Conv3Run {
+    int f0, frames;               // first frame and frame count
+    Conv3Plan plan;
+};
+std::vector<Conv3Run> conv3_runs(const Conv3Query& q);
 // the small-batch rule: conv3s when the product geometry gives fewer than cus workgroups and
 // conv3s supports the conv and gives more, but no more than kConv3sMaxPerCu per CU (measured: the
 // 64 x 32 tile is level with the 256-position tiles at 2.8 workgroups per CU and 1.8x slower at 5.7;
@@ -176,7 +195,7 @@ constexpr int kConv3sMaxPerCu = 4;
 // launched grid (border rows and strip overlap included: 308 / 340 workgroups) no longer fits one
 // round on 256 CUs -- 3.62 against 3.17 ms and 2.26 against 2.01 ms per forward
 constexpr int kConv7sBigPerCus = 4;
-// a.sw / a.nstrips checked against the plan; border, rcp and pbn set from it
+// the arguments a launcher hands its kernel: sw, nstrips, border, rcp and pbn set from the plan
 ConvArgs conv3_planned_args(const ConvArgs& a, const Conv3Plan& p);
 
 // launch-log names of the other conv kernels a net's conv can run in (the launchers log them with
@@ -185,11 +204,12 @@ constexpr char kConvImageKernel[] = "conv_image_kernel";
 constexpr char kConv1FusedKernel[] = "conv1_fused_kernel";
 constexpr char kConvHeadKernel[] = "conv_head_kernel";
 
-// conv3.hip: the public entry -- plans the conv and launches what the plan says.  Families conv3
+// conv3.hip: the public entry -- checks the arguments against the plan and launches what the plan
+// says (it does not plan: the caller's conv3_plan / conv3_runs did).  Families conv3
 // and conv3s are conv3_kernel itself: 7x7, 3x3 and 1x1 tiles of 8 / 16 waves and, for forwards too
 // small to fill the chip with those, 3x3 (any border) and 7x7 (border >= 3) tiles of 4 waves
 // (64 x 32 or 128 x 64; logged as conv3s_kernel<...>), bit-identical to the larger ones
-void launch_conv3(const ConvArgs& a, hipStream_t stream);
+void launch_conv3(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
 // conv3w.hip: the persistent 512 x {128, 96} 3x3 variant with one mid-unit barrier per K unit
 void launch_conv3w(const ConvArgs& a, const Conv3Plan& p, hipStream_t stream);
 // conv3w8.hip: the same tile with 8 waves of 64 x BN (fewer LDS fragment reads per MFMA)

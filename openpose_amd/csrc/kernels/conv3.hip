@@ -779,15 +779,14 @@ __global__ __launch_bounds__(64 * kP_NW, 1) void conv3p_kernel(const ConvArgs a)
 // reads stay inside the halo slot: BM + (KS - 1) * (VW + 1) <= HR (conv3_plan checks it).  The
 // last strip's columns past the image (nstrips * sw >= W) are masked by Strips::interior.
 //
-// The public entry: plans the conv (conv_plan.cpp decides kernel, tile, strips and grid) and
-// launches what the plan says; both families of conv3_kernel tiles (conv3 and conv3s, conv_tiles.h)
+// The public entry: launches what the caller's plan says (conv_plan.cpp decided kernel, tile,
+// strips and grid); both families of conv3_kernel tiles (conv3 and conv3s, conv_tiles.h)
 // take the one ladder below.
 // (a Winograd F(2,3)-along-x variant of the persistent kernel measured 15-50 % slower on every
 // BODY_25 layer -- LDS-read bound: 4 accumulators per output pair halve the wave tile, doubling
 // the fragment reads per MFMA; removed, source and numbers in profiles/round3/wino/)
-void launch_conv3(const ConvArgs& args, hipStream_t stream)
+void launch_conv3(const ConvArgs& args, const Conv3Plan& p, hipStream_t stream)
 {
-    const Conv3Plan p = conv3_plan(conv3_query(args));
     const char* fam = p.family == Conv3Family::conv3s ? "conv3s" : "conv3";
     ConvArgs a = args;
     a.wide = dev_switch("CONV3_WIDE", 1);

@@ -506,7 +506,8 @@ void launch_conv_head(const HeadArgs& a, hipStream_t stream)
     // 23 % slower (one per CU) or unchanged-slow (two per CU) -- profiles/round3/head/
     // Split precision: per-tile at both N1 (the persistent <512, 4, split> spills 10-14 VGPRs per
     // tile; measured 98.5 against 98.7 ms per 130-frame split forward, profiles/round6/split_head/)
-    const bool persist = a.cus > 0 && a.n1 == 512 && !a.split;
+    // (HEAD_PERSIST=0: one workgroup per tile, dev A/B)
+    const bool persist = a.cus > 0 && a.n1 == 512 && !a.split && dev_switch("HEAD_PERSIST", 1) != 0;
     const unsigned G = (unsigned)(persist ? std::min<long>(a.cus, ntiles) : ntiles);
     const dim3 blk(64 * kH_NW);
 #define OPKH_LAUNCH3(N1_, NF2_, MX_, SP_)                                                       \

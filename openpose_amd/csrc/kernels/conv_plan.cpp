@@ -1,6 +1,6 @@
-// conv_plan.cpp -- which kernel runs a 7x7 / 3x3 / 1x1 conv, on which tile, strips and grid: the
-// one decider behind NetHip's planner and frame runs, the launchers of conv3.hip, conv3w.hip,
-// conv3w8.hip, opk_net_conv_plan and opk_net_conv_kernels (conv.h).  Plain host
+// conv_plan.cpp -- which kernel runs a 7x7 / 3x3 / 1x1 conv, on which tile, strips and grid, in
+// which frame runs: the one decider behind NetHip's planner (so behind its launch list,
+// opk_net_conv_plan and opk_net_conv_kernels) and the probe tools (conv.h).  Plain host
 // code: no HIP calls, so the decision is testable without a GPU.
 #include "conv.h"
 
@@ -326,29 +326,34 @@ Conv3Plan conv3_plan(const Conv3Query& query, int only)
     return s;
 }
 
-int conv3_run_frames(const Conv3Query& query)
+std::vector<Conv3Run> conv3_runs(const Conv3Query& query)
 {
     Conv3Query q = query;
-    auto fits = [&](int frames) {
+    auto plan = [&](int frames) {
         q.frames = frames;
-        return conv3_plan(q).fits;
+        return conv3_plan(q);
     };
     const int n = query.frames;
-    if (fits(n)) return n;
-    for (int runs = 2;; ++runs) {   // the fewest even runs whose every run fits
-        const int run = (n + runs - 1) / runs;
+    int run = n;
+    for (int runs = 1;; ++runs) {   // the fewest even runs whose every run fits
+        run = (n + runs - 1) / runs;
         const int last = n - ((n + run - 1) / run - 1) * run;
-        if (fits(run) && fits(last)) return run;
+        if (plan(run).fits && plan(last).fits) break;
         OPK_CHECK_ARG(run > 1, "one frame exceeds a launch's position range");
     }
+    std::vector<Conv3Run> out;
+    for (int f0 = 0; f0 < n; f0 += run)
+        out.push_back(Conv3Run{f0, std::min(run, n - f0), plan(std::min(run, n - f0))});
+    return out;
 }
 
 ConvArgs conv3_planned_args(const ConvArgs& a, const Conv3Plan& p)
 {
     ConvArgs b = a;
     if (b.border <= 0) b.border = 1;
-    OPK_CHECK_ARG(a.sw == p.sw && a.nstrips == p.nstrips, "strip geometry differs from conv3_plan");
     OPK_CHECK_ARG(p.fits, "too many positions per launch");
+    b.sw = p.sw;
+    b.nstrips = p.nstrips;
     for (int i = 0; i < 3; ++i) b.rcp[i] = p.rcp[i];
     if (p.family == Conv3Family::conv3s) b.pbn = p.pbn;
     return b;

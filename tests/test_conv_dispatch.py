@@ -121,9 +121,11 @@ def agrees(net, shape, recorded_name):
     ("front", (4, 184, 328), False, dict(CONV1_FUSED=0)),
     ("front", (4, 184, 328), True, dict(CONV1_FUSED=0))], ids=["variants", "front-fp16", "front-split"])
 def test_asked_again_after_a_switch_flips(host, model, shape, split, fixed):
-    """One net, planned under the defaults, asked again while a decision switch is flipped: the
-    recorded answer of that switch set, and the defaults' answer again afterwards (the switches
-    are read per query, as the launchers read them per launch)."""
+    """One net asked again while a decision switch is flipped: the recorded answer of that
+    switch set, and the defaults' answer again afterwards.  The switches are read per query (every
+    conv_kernels / conv_plan call plans afresh on the host).  A forward is another matter: it
+    replays the launches planned when its input shape was first seen, under the switches of that
+    moment (tests/test_gpu_conv_dispatch.py)."""
     def name(**switches):
         return case(model, shape, split, **switches)["name"]
 
@@ -138,6 +140,46 @@ def test_asked_again_after_a_switch_flips(host, model, shape, split, fixed):
                 with dev_switches(**flip):
                     agrees(net, shape, name(**fixed, **flip))
                 agrees(net, shape, name(**fixed))
+    finally:
+        net.close()
+
+
+@pytest.mark.parametrize("shape,split,small", [((FRAME_RUN_BATCH, 368, 656), True, False),
+                                               ((1, 368, 656), False, True)], ids=["frame-runs", "small"])
+def test_one_kernel_name_per_frame_run(host, shape, split, small):
+    """The run list as data: conv_kernels gives one name per frame run of a conv that launches a
+    halo kernel -- k names stand for k even runs of ceil(n / k) frames, the last one the rest --
+    each name what a fresh query at that run's frame count gives on its own (name and tile), and
+    no smaller number of even runs fits a launch's position range."""
+    n, h, w = shape
+    net = Net(host, BODY_25)
+    try:
+        if split:
+            net.set_precision(PRECISION_SPLIT)
+        if small:
+            net.set_small_batch(True)
+        several = []
+        for i, c in enumerate(net.convs()):
+            got = net.conv_kernels(i, n, h, w, CUS)
+            if not got or got[0] in BARE:   # inside / as a fused kernel, the image conv: no runs
+                continue
+            run = -(-n // len(got))
+            frames = [min(run, n - f0) for f0 in range(0, n, run)]
+            assert len(frames) == len(got), (c["name"], got, frames)
+            for name, f in zip(got, frames):
+                assert net.conv_kernels(i, f, h, w, CUS) == [name], (c["name"], f, got)
+                p = net.conv_plan(i, f, h, w, CUS)
+                assert (p["bm"], p["bn"], p["small"]) == tile_of(name), (c["name"], f, name, p)
+            for fewer in range(1, len(got)):
+                size = -(-n // fewer)
+                last = n - (-(-n // size) - 1) * size
+                assert any(len(net.conv_kernels(i, f, h, w, CUS)) > 1 for f in (size, last)), (c["name"], fewer)
+            if len(got) > 1:
+                several.append(c["name"])
+        assert several == (["conv1_2"] if n == FRAME_RUN_BATCH else [])
+        if small:
+            assert any(k.startswith("conv3s_kernel<") for i in range(len(net.convs()))
+                       for k in net.conv_kernels(i, n, h, w, CUS))
     finally:
         net.close()
 

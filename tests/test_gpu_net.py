@@ -612,7 +612,7 @@ def test_split_precision_blobs_and_graphs(ctx):
 def test_split_precision_large_batch_frame_runs(ctx):
     """Split precision at a batch whose full-resolution layers exceed one conv3 launch's 24-bit
     position range (70 x 370 x 658 padded positions): the convs run in frame runs
-    (launch_conv3_frames), and every frame's output equals the same frame forwarded alone, bit for
+    (conv3_runs), and every frame's output equals the same frame forwarded alone, bit for
     bit (an output's MFMA accumulation order does not depend on the batch)."""
     from openpose_amd.api import PRECISION_SPLIT
     n = 70

@@ -98,8 +98,6 @@ int main(int argc, char** argv)
     CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
     a.cus = cus;
     const Conv3Plan s3 = conv3_plan(conv3_query(a));   // (OPK_CONV3_PERSIST=0: conv3_kernel, the stamped one)
-    a.sw = s3.sw;
-    a.nstrips = s3.nstrips;
     const int nblk = (int)s3.grid;
     CK(hipMalloc(&dst, (size_t)nblk * 8 * 8));
     CK(hipMemset(dst, 0, (size_t)nblk * 8 * 8));
@@ -108,10 +106,10 @@ int main(int argc, char** argv)
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i) launch_conv3(a, 0);
+    for (int i = 0; i < 3; ++i) launch_conv3(a, s3, 0);
     CK(hipDeviceSynchronize());
     CK(hipEventRecord(e0, 0));
-    for (int i = 0; i < iters; ++i) launch_conv3(a, 0);
+    for (int i = 0; i < iters; ++i) launch_conv3(a, s3, 0);
     CK(hipEventRecord(e1, 0));
     CK(hipEventSynchronize(e1));
     float ms = 0;

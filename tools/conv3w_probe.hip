@@ -100,8 +100,8 @@ int main(int argc, char** argv)
     a.sink = dsink;
     CK(hipDeviceGetAttribute(&a.cus, hipDeviceAttributeMultiprocessorCount, 0));
     a.border = 1;
-    a.sw = W;          // one strip (W + 2 <= 87 for the 688-row halo)
-    a.nstrips = 1;     // (the launchers hold both against conv3_plan and set the reciprocals)
+    // (one strip: W + 2 <= 87 for the 688-row halo; the launchers set sw / nstrips and the
+    // reciprocals from the plan)
     const long ntm = (pos + 511) / 512;
     const int G = (int)std::min<long>(a.cus, ntm);
     unsigned long long* dst;
