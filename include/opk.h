@@ -886,7 +886,8 @@ int opk_pose_read_track_times(opk_pose* pose, int* batches, double* pyramid_ms, 
  * op::WPoseTriangulation (--3d; include/openpose/3d/wPoseTriangulation.hpp:62-100,
  * src/openpose/3d/poseTriangulation.cpp:8-166, src/openpose/3d/poseTriangulationPrivate.cpp:11-33,
  * 119-226), the reference's default build: the USE_CERES refinement (poseTriangulationPrivate.cpp:
- * 228-290) is out of scope, as are the calibration files, --frame_undistort and the 3-D renderer.
+ * 228-290) is out of scope, as is the 3-D renderer; the calibration files and --frame_undistort
+ * are the section after this one.
  * The reference takes the null vector of each point's matrix from OpenCV's cv::SVD; OpenCV is not
  * here, so this text is the definition -- a one-sided Jacobi of the form cv::SVD's JacobiSVDImpl_
  * has -- and parity with cv::SVD is by restatement only (tests/triangulate_cases.py, which is also
@@ -986,6 +987,119 @@ int opk_triangulate(opk_ctx* ctx, const opk_rig* rig, int steps, int parts,
 #define OPK_3D_HAND_RIGHT 3
 int opk_pose_set_views(opk_pose* pose, const opk_rig* rig);
 int opk_pose_keypoints_3d(opk_pose* pose, int step, int kind, float* xyz_host, int* status);
+
+/* ---- Undistorted rig frames and the calibration files: op::CameraParameterReader
+ * (include/openpose/3d/cameraParameterReader.hpp; readParameters, src/openpose/3d/
+ * cameraParameterReader.cpp:85-173, and undistort, :337-399, which the producer runs on every frame
+ * under --frame_undistort, producer.cpp:115-119): cv::initUndistortRectifyMap(K, dist, I, K, size,
+ * CV_16SC2) once per camera and cv::remap(INTER_LINEAR, constant border 0) per frame.  OpenCV is
+ * not here, so this text is the definition -- OpenCV 4.2's scalar path with those arguments (R the
+ * identity, the new camera matrix K itself) -- and parity with OpenCV is by restatement only
+ * (tests/undistort_cases.py, which is also held against an evaluation without the row
+ * accumulation in extended precision).  Every operation below is fp64 and rounded on its own.
+ *
+ * CAMERAS (opk_cameras).  V >= 1 views; per view intrinsics K[3][3] row-major, ncoef distortion
+ *   coefficients, ncoef in {4, 5, 8, 12}, in the order k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 (the
+ *   absent ones are 0; view v's start at distortions[12 * v]), and an image size (w, h).
+ *   OPK_ERR_ARG: V < 1, an entry that is not finite, any other ncoef, a singular K (the
+ *   determinant below is 0) or a size <= 0.  ncoef = 14 (the tilted-sensor model) is
+ *   OPK_ERR_UNSUPPORTED.
+ *
+ * THE MAP OF ONE CAMERA, m1 [h][w][2] int16 and m2 [h][w] uint16.
+ *   ir = the inverse of K by the 3x3 closed form:
+ *     det = K00*(K11*K22 - K12*K21) - K01*(K10*K22 - K12*K20) + K02*(K10*K21 - K11*K20), d = 1/det,
+ *     ir[0] = (K11*K22 - K12*K21)*d   ir[1] = (K02*K21 - K01*K22)*d   ir[2] = (K01*K12 - K02*K11)*d
+ *     ir[3] = (K12*K20 - K10*K22)*d   ir[4] = (K00*K22 - K02*K20)*d   ir[5] = (K02*K10 - K00*K12)*d
+ *     ir[6] = (K10*K21 - K11*K20)*d   ir[7] = (K01*K20 - K00*K21)*d   ir[8] = (K00*K11 - K01*K10)*d
+ *   With fx = K00, fy = K11, u0 = K02, v0 = K12, row i starts at _x = i*ir[1] + ir[2],
+ *   _y = i*ir[4] + ir[5], _w = i*ir[7] + ir[8], and after each column _x += ir[0], _y += ir[3],
+ *   _w += ir[6]: the accumulation along the row is part of the definition.  At column j
+ *     w = 1/_w;  x = _x*w;  y = _y*w;  x2 = x*x;  y2 = y*y;  r2 = x2 + y2;  _2xy = 2*x*y;
+ *     kr = (1 + ((k3*r2 + k2)*r2 + k1)*r2) / (1 + ((k6*r2 + k5)*r2 + k4)*r2);
+ *     xd = x*kr + p1*_2xy + p2*(r2 + 2*x2) + s1*r2 + s2*r2*r2;
+ *     yd = y*kr + p1*(r2 + 2*y2) + p2*_2xy + s3*r2 + s4*r2*r2;
+ *     u = fx*xd + u0;  v = fy*yd + v0
+ *   (sums and products left to right).  iu = round_half_even(u*32) and iv likewise, as int32; a
+ *   product that is NaN or rounds outside the int32 range gives INT_MIN, as x86's conversion
+ *   does.  m1[i][j] = ((short)(iu >> 5), (short)(iv >> 5)), the shift arithmetic and the short
+ *   the low 16 bits; m2[i][j] = (uint16)((iv & 31)*32 + (iu & 31)).
+ *
+ * THE REMAP OF ONE FRAME, BGR uint8, constant border 0.  For the destination pixel (x, y):
+ *   (sx, sy) = m1[y][x], f = m2[y][x], wt = T[f >> 5][f & 31] -- the 2x2 int16 weights of the
+ *   bilinear fixed-point table of the frame warp (initInterTab2D(INTER_LINEAR, fixpt); sum 32768)
+ *   -- and per channel
+ *     D = (S(sy, sx)*wt00 + S(sy, sx+1)*wt01 + S(sy+1, sx)*wt10 + S(sy+1, sx+1)*wt11 + 16384) >> 15
+ *   with S = 0 at any tap outside the frame: what remapBilinear computes on both of its paths.
+ *   NV12 / I420 sources: the result is the remap of opk_frames_to_bgr(frames); every tap is
+ *   converted as it is read and no BGR copy of the source is made.
+ *
+ * WHICH CAMERA.  Frame f uses view f % V, the rule of opk_pose_set_views.  The reference builds
+ *   every camera's map from camera 0's intrinsics and distortion (cameraParameterReader.cpp:
+ *   354-355); this interface takes each view's own: passing camera 0's for every view reproduces
+ *   the reference.
+ *
+ * opk_undistort_maps_host: a pure host function (no context): the map of one view, m1_host
+ *   [h][w][2], m2_host [h][w].
+ * opk_undistort_frames: src (n frames of any format) -> dst (BGR, the same n and size), enqueued on
+ *   the context's stream: kernels/undistort.hip, one launch per view over the view's frames.  The
+ *   maps are built on the host and uploaded on the first use of a camera set; the context keeps
+ *   them, keyed by the parameters' bytes.  OPK_ERR_ARG, before any device work: a destination that
+ *   is not BGR, n not a multiple of V, a frame size other than its view's, every descriptor error
+ *   and overlap rule of opk_frames / opk_frames_out (opk_render_frames_to); n == 0 succeeds
+ *   without device work.  The cached maps are never evicted: every distinct camera set keeps its
+ *   6 bytes per pixel and distinct camera (5.5 MB per camera at 1280x720) until opk_ctx_destroy --
+ *   meant for a fixed rig, not for parameters that change from call to call. */
+typedef struct opk_cameras {
+    int views;                  /* V */
+    const double* intrinsics;   /* [V][3][3] */
+    const double* distortions;  /* [V][12]: the first ncoef[v] of a row are read */
+    const int* ncoef;           /* [V]: 4, 5, 8 or 12 */
+    const int* image_sizes;     /* [V][2]: width, height */
+} opk_cameras;
+int opk_undistort_maps_host(const opk_cameras* cams, int view, int16_t* m1_host, uint16_t* m2_host);
+int opk_undistort_frames(opk_ctx* ctx, const opk_frames_out* dst, const opk_frames* src,
+                         const opk_cameras* cams);
+/* The undistortion as the first stage of the raw-frame pipeline (--frame_undistort), under the
+ * attach rules of opk_pose_attach_tracker: setting or clearing (cams NULL) with batches in flight
+ * is OPK_ERR_STATE; the struct is copied.  While set, opk_pose_submit_frames first undistorts the
+ * batch into a BGR buffer the batch's slot owns (it grows on demand; two slots, the two batches in
+ * flight: 130 frames of 1280x720 are 360 MB per slot), and the frame warp, the tracker's pyramid,
+ * the face / hand crops and the rig's size check read that buffer.  n not a multiple of V or a frame
+ * size other than its view's is OPK_ERR_ARG at submit, before any device work.  Composes with
+ * opk_pose_set_views (frame f is view f % V for both).
+ * opk_pose_undistorted_frames: the description of the collected batch's buffer -- valid until the
+ * second submit after that batch's, or until the cameras are cleared, which frees both slots'
+ * buffers; hand it to the renders so the skeletons land on the undistorted image.  OPK_ERR_STATE
+ * without cameras or without a batch collected with them. */
+int opk_pose_set_undistort(opk_pose* pose, const opk_cameras* cams);
+int opk_pose_undistorted_frames(opk_pose* pose, opk_frames* out);
+/* The calibration files: <dir>/<serial>.xml as the reference's writer emits them
+ * (models/cameraParameters/flir/17012332.xml.example) -- an <opencv_storage> element whose children
+ * CameraMatrix (3x4, the extrinsics), Intrinsics (3x3), Distortion (N x 1 or 1 x N, N in {4, 5, 8,
+ * 12, 14}) and the optional CameraMatrixInitial (3x4) hold <rows>, <cols>, <dt> (d or f) and
+ * whitespace-separated <data>; comments and the <?xml?> line are skipped.  Not a general XML
+ * parser.  serials NULL: every *.xml of the directory, sorted by name (getFilesOnDirectory), n
+ * ignored.  out [capacity] (NULL with capacity 0 to ask for *count alone); more cameras than
+ * capacity is OPK_ERR_ARG.  camera_matrix is opk_camera_matrix(intrinsics, extrinsics).  A pure
+ * host function.  OPK_ERR_ARG with the reference's wording -- "Error at reading the camera matrix
+ * parameters of the camera with serial number `S` (file: P.xml). Is its format valid? You might
+ * want to check the example xml file.", likewise "camera intrinsics parameters", "camera distortion
+ * parameters" and, for a file that cannot be opened or holds no <opencv_storage>, "camera
+ * parameters"; a missing CameraMatrixInitial is no error (has_initial 0, extrinsics_initial the
+ * 3x4 identity).  A count that disagrees with rows x cols, or a number strtod does not consume
+ * whole, is OPK_ERR_ARG with the file named. */
+typedef struct opk_camera_parameters {
+    char serial[256];
+    double extrinsics[12];           /* CameraMatrix */
+    double intrinsics[9];
+    double distortion[14];           /* the first ncoef as read, zeros after */
+    int ncoef;
+    int has_initial;
+    double extrinsics_initial[12];   /* CameraMatrixInitial */
+    double camera_matrix[12];        /* intrinsics x extrinsics */
+} opk_camera_parameters;
+int opk_camera_parameters_read(const char* dir, const char* const* serials, int n,
+                               opk_camera_parameters* out, int capacity, int* count);
 
 /* ---- Measured ceilings (no reference counterpart; SURVEY.md §8d "confirm the vendor peaks"):
  *      dense fp16 MFMA rate of v_mfma_f32_16x16x32_f16 from registers (the conv kernels'

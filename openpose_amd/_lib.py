@@ -194,6 +194,12 @@ _SIGS = {
     "opk_triangulate": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
     "opk_pose_set_views": (_i, [_p, _p]),
     "opk_pose_keypoints_3d": (_i, [_p, _i, _i, _p, _ip]),
+    # undistorted rig frames and the calibration files (CamerasStruct, CameraParametersStruct)
+    "opk_undistort_maps_host": (_i, [_p, _i, _p, _p]),
+    "opk_undistort_frames": (_i, [_p, _p, _p, _p]),
+    "opk_pose_set_undistort": (_i, [_p, _p]),
+    "opk_pose_undistorted_frames": (_i, [_p, _p]),
+    "opk_camera_parameters_read": (_i, [_c.c_char_p, _c.POINTER(_c.c_char_p), _i, _p, _i, _ip]),
 }
 
 
@@ -206,6 +212,19 @@ class FramesStruct(ctypes.Structure):
 class RigStruct(ctypes.Structure):
     """opk_rig (include/opk.h)."""
     _fields_ = [("views", _i), ("camera_matrices", _p), ("image_sizes", _p), ("min_views", _i)]
+
+
+class CamerasStruct(ctypes.Structure):
+    """opk_cameras (include/opk.h)."""
+    _fields_ = [("views", _i), ("intrinsics", _p), ("distortions", _p), ("ncoef", _p),
+                ("image_sizes", _p)]
+
+
+class CameraParametersStruct(ctypes.Structure):
+    """opk_camera_parameters (include/opk.h)."""
+    _fields_ = [("serial", _c.c_char * 256), ("extrinsics", _d * 12), ("intrinsics", _d * 9),
+                ("distortion", _d * 14), ("ncoef", _i), ("has_initial", _i),
+                ("extrinsics_initial", _d * 12), ("camera_matrix", _d * 12)]
 
 
 class FramesOutStruct(ctypes.Structure):

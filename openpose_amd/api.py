@@ -6,6 +6,7 @@ reference operators they replace (include/opk.h lists the reference file:line of
 """
 import atexit
 import ctypes
+import os
 import weakref
 
 import numpy as np
@@ -325,6 +326,19 @@ class Context:
         self.h = h
         _LIVE["ctx"].add(self)
         return self
+
+    def undistort_frames(self, frames, cameras, out=None):
+        """opk_undistort_frames: the frames -- uint8 [n, h, w, 3] (CUDA) or a Frames (BGR, NV12,
+        I420) -- undistorted, frame f through the maps of view f % V of `cameras` (a Cameras), as
+        BGR uint8 [n, h, w, 3] (or into `out`: such a tensor, [n, h, row bytes], or a BGR Frames)."""
+        src = _as_frames(frames)
+        if out is None:
+            out = torch.empty((src.n, src.height, src.width, 3), dtype=torch.uint8,
+                              device=src.device)
+        dst = out if isinstance(out, Frames) else Frames.bgr(out, src.width)
+        s, d, c = src.struct(), dst.struct_out(), cameras.struct()
+        check(self.L.opk_undistort_frames(self.h, ctypes.byref(d), ctypes.byref(s), ctypes.byref(c)))
+        return out
 
     # ---- person ids across frames -------------------------------------------------------------
     def pyramid(self, frames, levels=3):
@@ -948,6 +962,106 @@ class Triangulator:
                 dropped.cpu().numpy())
 
 
+class Cameras:
+    """The lenses of a rig for the undistortion (opk_cameras, include/opk.h): intrinsics [V, 3, 3],
+    distortions a list of V coefficient vectors of 4, 5, 8 or 12 values each (k1 k2 p1 p2 k3 k4 k5
+    k6 s1 s2 s3 s4), image_sizes [V, 2] (width, height).  Frame f of a batch uses view f % V.  The
+    reference builds every camera's map from camera 0's parameters; pass camera 0's for every view
+    to reproduce that.  The library checks the values where they are used (maps,
+    Context.undistort_frames, PoseExtractor.set_undistort): OPK_ERR_ARG / OPK_ERR_UNSUPPORTED."""
+
+    def __init__(self, intrinsics, distortions, image_sizes):
+        self.K = np.ascontiguousarray(intrinsics, np.float64)
+        if self.K.ndim != 3 or self.K.shape[1:] != (3, 3):
+            raise ValueError("intrinsics [V, 3, 3]")
+        self.views = self.K.shape[0]
+        dist = [np.asarray(d, np.float64).reshape(-1) for d in distortions]
+        self.sizes = np.ascontiguousarray(image_sizes, np.int32)
+        if len(dist) != self.views or self.sizes.shape != (self.views, 2):
+            raise ValueError("one distortion vector and one (width, height) per view")
+        self.ncoef = np.array([d.size for d in dist], np.int32)
+        self.dist = np.zeros((self.views, 12), np.float64)
+        for v, d in enumerate(dist):
+            self.dist[v, :min(d.size, 12)] = d[:12]
+
+    def struct(self):
+        return _lib.CamerasStruct(self.views, self.K.ctypes.data, self.dist.ctypes.data,
+                                  self.ncoef.ctypes.data, self.sizes.ctypes.data)
+
+    def maps(self, view):
+        """opk_undistort_maps_host: (m1 int16 [h, w, 2], m2 uint16 [h, w]) of one view."""
+        if not 0 <= view < self.views:
+            raise ValueError("bad view")
+        w, h = int(self.sizes[view, 0]), int(self.sizes[view, 1])
+        m1 = np.zeros((h, w, 2), np.int16)
+        m2 = np.zeros((h, w), np.uint16)
+        s = self.struct()
+        check(_lib.load().opk_undistort_maps_host(ctypes.byref(s), view,
+                                                  m1.ctypes.data_as(ctypes.c_void_p),
+                                                  m2.ctypes.data_as(ctypes.c_void_p)))
+        return m1, m2
+
+
+class CameraParameters:
+    """The calibration files of a rig (op::CameraParameterReader::readParameters): one
+    <dir>/<serial>.xml per camera.  serials: the cameras in rig order, one of them .intrinsics
+    [V, 3, 3], .distortions (a list of V vectors), .extrinsics [V, 3, 4] (the files' CameraMatrix),
+    .extrinsics_initial [V, 3, 4] (CameraMatrixInitial, the identity where a file has none) and
+    .camera_matrices [V, 3, 4] = intrinsics x extrinsics."""
+
+    def __init__(self, serials, intrinsics, distortions, extrinsics, extrinsics_initial,
+                 camera_matrices):
+        self.serials, self.intrinsics, self.distortions = serials, intrinsics, distortions
+        self.extrinsics, self.extrinsics_initial = extrinsics, extrinsics_initial
+        self.camera_matrices = camera_matrices
+
+    @classmethod
+    def read(cls, directory, serials=None):
+        """opk_camera_parameters_read; serials None: every *.xml of the directory, sorted."""
+        L = _lib.load()
+        d = os.fsencode(str(directory))
+        count = ctypes.c_int(0)
+        if serials is None:
+            names, n = None, 0
+            check(L.opk_camera_parameters_read(d, None, 0, None, 0, ctypes.byref(count)))
+        else:
+            n = len(serials)
+            names = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(str(x)) for x in serials])
+            count.value = n
+        out = (_lib.CameraParametersStruct * max(count.value, 1))()
+        check(L.opk_camera_parameters_read(d, names, n, ctypes.byref(out), count.value,
+                                           ctypes.byref(count)))
+        cams = [out[i] for i in range(count.value)]
+        arr = lambda field, shape: np.array([list(getattr(c, field)) for c in cams],
+                                            np.float64).reshape((len(cams),) + shape)
+        return cls([os.fsdecode(c.serial) for c in cams], arr("intrinsics", (3, 3)),
+                   [np.array(list(c.distortion)[:c.ncoef], np.float64) for c in cams],
+                   arr("extrinsics", (3, 4)), arr("extrinsics_initial", (3, 4)),
+                   arr("camera_matrix", (3, 4)))
+
+    def _sizes(self, image_sizes):
+        sizes = np.asarray(image_sizes, np.int32)
+        if sizes.shape == (2,):
+            sizes = np.tile(sizes, (len(self.serials), 1))
+        return sizes
+
+    def triangulator(self, image_sizes, min_views=-1):
+        """The Triangulator of these cameras; image_sizes [V, 2] or one (width, height) for all."""
+        return Triangulator(self.camera_matrices, self._sizes(image_sizes), min_views)
+
+    def cameras(self, image_sizes):
+        """The Cameras (undistortion) of these cameras, each view with its own parameters."""
+        return Cameras(self.intrinsics, self.distortions, self._sizes(image_sizes))
+
+
+class _DeviceBytes:
+    """Library-owned device memory as a uint8 tensor (torch.as_tensor reads this interface)."""
+
+    def __init__(self, ptr, shape, strides):
+        self.__cuda_array_interface__ = {"shape": shape, "typestr": "|u1", "data": (ptr, False),
+                                         "version": 2, "strides": strides}
+
+
 class Net:
     """op::NetCaffe replacement (NetHip): prototxt path or "builtin:BODY_25"."""
 
@@ -1145,6 +1259,7 @@ class PoseExtractor:
         self._attached = {}   # kind -> KeypointExtractor (kept alive while attached)
         self._tracker = None  # the attached Tracker
         self._views = None    # the Triangulator of set_views
+        self._undistort = None   # the Cameras of set_undistort
 
     def close(self):
         if self.h:
@@ -1215,6 +1330,31 @@ class PoseExtractor:
                                                    ctypes.byref(st)))
             out.append(xyz if st.value else np.zeros((0, parts, 4), np.float32))
         return out
+
+    # ---- undistortion (opk_pose_set_undistort) -------------------------------------------------
+    def set_undistort(self, cameras):
+        """A Cameras: from now on submit_frames / forward_frames first undistort the batch (frame f
+        through view f % V) into a BGR buffer of the batch's slot, and every later stage -- the
+        warp, the tracker, the face / hand crops -- reads that; undistorted_frames() hands it out
+        for the renders.  None clears and frees the slots' buffers.  Not with batches in flight.
+        130 frames of 1280x720 are 360 MB per slot, two slots; the context keeps the maps of every
+        distinct camera set it has seen (5.5 MB per camera at 1280x720) until it is closed."""
+        if cameras is None:
+            check(self.L.opk_pose_set_undistort(self.h, None))
+        else:
+            c = cameras.struct()
+            check(self.L.opk_pose_set_undistort(self.h, ctypes.byref(c)))
+        self._undistort = cameras
+
+    def undistorted_frames(self):
+        """The collected batch's undistorted frames as a BGR Frames over the pipeline's buffer (no
+        copy): valid until the second submit after that batch's or set_undistort(None)."""
+        f = _lib.FramesStruct()
+        check(self.L.opk_pose_undistorted_frames(self.h, ctypes.byref(f)))
+        step, frame = int(f.step[0]), int(f.frame_bytes[0])
+        t = torch.as_tensor(_DeviceBytes(int(f.plane[0]), (f.n, f.height, f.width * 3),
+                                         (frame, step, 1)), device="cuda")
+        return Frames.bgr(t, f.width)
 
     def person_ids(self, frame):
         """int64 [people] ids of a collected frame, person order of keypoints() (needs a tracker)."""

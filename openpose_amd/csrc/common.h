@@ -65,6 +65,11 @@ struct DevBuf {
         }
         return ptr;
     }
+    void release() {
+        if (ptr) OPK_HIP(hipFree(ptr));
+        ptr = nullptr;
+        bytes = 0;
+    }
     ~DevBuf() { if (ptr) (void)hipFree(ptr); }
 };
 

@@ -1157,6 +1157,35 @@ int opk_pose_keypoints_3d(opk_pose* p, int step, int kind, float* xyz_host, int*
     });
 }
 
+int opk_pose_set_undistort(opk_pose* p, const opk_cameras* cams)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        if (!cams) {
+            p->pose->set_undistort(nullptr);
+            return;
+        }
+        const opk::UndistortCameras c = opk::make_cameras(cams);
+        p->pose->set_undistort(&c);
+    });
+}
+
+int opk_pose_undistorted_frames(opk_pose* p, opk_frames* out)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p && out, "NULL argument");
+        const opk::FrameSource& f = p->pose->undistorted_frames();
+        *out = opk_frames{};
+        out->format = OPK_FRAMES_BGR;
+        out->n = f.n;
+        out->width = f.w;
+        out->height = f.h;
+        out->plane[0] = f.plane[0];
+        out->step[0] = f.step;
+        out->frame_bytes[0] = f.frame[0];
+    });
+}
+
 int opk_pose_read_track_times(opk_pose* p, int* batches, double* pyramid_ms, double* lk_ms,
                               double* host_ms)
 {

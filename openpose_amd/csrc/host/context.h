@@ -10,6 +10,7 @@
 #include "../common.h"
 #include "../kernels/kernels.h"
 #include "pose_model.h"
+#include "undistort.h"
 
 struct opk_render_layer;   // include/opk.h
 struct opk_render_heat;
@@ -61,6 +62,12 @@ struct Context {
     int* nms_candidates(int frames, int parts);
     HostBuf host_peaks, host_scores;
     DevBuf tri_errors;       // opk_triangulate without errors_dev: the points' errors
+
+    // undistortion (host/undistort_dev.cpp): the device maps of every camera set seen, keyed by the
+    // parameters' bytes; views with equal parameters share one pair of maps
+    struct UndistortDev { DevBuf buf; std::vector<UndistortMap> view; };
+    std::map<std::string, std::unique_ptr<UndistortDev>> undistort_maps;
+    const UndistortDev& undistort_dev(const UndistortCameras& cams);
 
     // streams other objects of this context run device work on besides `stream` (PoseHip's
     // post-processing stream, its multi-scale net streams): opk_sync waits for them too

@@ -336,6 +336,23 @@ void PoseHip::set_views(const TriRig* rig)
     v3d_valid_ = false;
 }
 
+void PoseHip::set_undistort(const UndistortCameras* cams)
+{
+    if (count_ != 0) throw Error(3, "batches in flight: collect them before setting the cameras");
+    undist_ = cams ? *cams : UndistortCameras{};
+    undist_valid_ = false;
+    undist_out_ = FrameSource{};
+    if (!cams)   // cleared: the slots' buffers (360 MB each at 130 frames of 1280x720) go back
+        for (Slot& sl : slots_) sl.undist.release();
+}
+
+const FrameSource& PoseHip::undistorted_frames() const
+{
+    if (!undistort_set()) throw Error(3, "no cameras set");
+    if (!undist_valid_) throw Error(3, "no collected batch with undistorted frames");
+    return undist_out_;
+}
+
 void PoseHip::check_views(int n, int w, int h) const
 {
     if (!views_set()) return;
@@ -584,14 +601,39 @@ void PoseHip::set_input(int net_w, int net_h, float dyn, int scale_number, doubl
     scale_gap_ = scale_gap;
 }
 
-void PoseHip::submit_frames(const FrameSource& frames)
+void PoseHip::submit_frames(const FrameSource& decoded)
 {
-    const int n = frames.n, w = frames.w, h = frames.h;
+    const int n = decoded.n, w = decoded.w, h = decoded.h;
     OPK_CHECK_ARG(net_ != nullptr, "no network: raw frames need the net");
-    OPK_CHECK_ARG(frames.plane[0] != nullptr && n > 0 && w > 0 && h > 0, "empty frames");
+    OPK_CHECK_ARG(decoded.plane[0] != nullptr && n > 0 && w > 0 && h > 0, "empty frames");
     OPK_CHECK_ARG(count_ < 2, "two batches already in flight: collect first");
     OPK_CHECK_ARG(model_ != 6, "BODY_19N (DenseNet normalisation) is not supported");
     check_views(n, w, h);
+    FrameSource frames = decoded;
+    if (undistort_set()) {
+        // the first stage: the batch undistorted into its slot's BGR buffer, which every later
+        // stage reads in place of the decoder's frames
+        check_cameras(undist_, n, w, h);
+        check_frames(decoded);
+        ctx_->bind();
+        FrameDest d{};
+        d.format = kFramesBgr;
+        d.n = n;
+        d.w = w;
+        d.h = h;
+        d.step = (size_t)w * 3;
+        d.frame[0] = d.step * h;
+        d.plane[0] = static_cast<uint8_t*>(slots_[(head_ + count_) & 1].undist.get(d.frame[0] * n));
+        undistort_frames(ctx_, d, decoded, undist_, ctx_->stream);
+        frames = FrameSource{};
+        frames.format = kFramesBgr;
+        frames.n = n;
+        frames.w = w;
+        frames.h = h;
+        frames.plane[0] = d.plane[0];
+        frames.step = d.step;
+        frames.frame[0] = d.frame[0];
+    }
     double scales[kMaxResizeSources];
     scale_and_size(w, h, in_net_w_, in_net_h_, dyn_, scale_number_, scale_gap_, scales, input_hw_);
     const float* ptrs[kMaxResizeSources];
@@ -952,6 +994,9 @@ int PoseHip::collect()
     hw_ = sl.W;
     scale_net_to_output_ = sl.scale;
     heat_valid_ = false;
+    // the undistorted frames of this batch: its slot's buffer (submit_frames)
+    undist_valid_ = undistort_set() && sl.raw.plane[0] != nullptr && sl.raw.plane[0] == sl.undist.ptr;
+    undist_out_ = undist_valid_ ? sl.raw : FrameSource{};
     run_parts(sl);   // the attached face / hand extractors, on this batch's frames
     run_views(sl);   // the rig: 3-D arrays of this batch's time steps
     run_tracker(sl, si);   // the attached tracker: LK and matching of this batch's frames

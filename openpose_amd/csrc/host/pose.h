@@ -10,6 +10,7 @@
 #include "pool.h"
 #include "track.h"
 #include "triangulate.h"
+#include "undistort.h"
 
 namespace opk {
 
@@ -146,6 +147,18 @@ public:
     // [parts][4] and the status of one step of the last collected batch; kind 0 body, 1 face,
     // 2 left hand, 3 right hand (an OPK_ERR_STATE error without views, batch or that extractor)
     const float* keypoints_3d(int step, int kind, int* parts, int* status) const;
+    // Undistortion (the reference's --frame_undistort, which its producer runs on every frame
+    // before any worker sees it): while cameras are set, submit_frames first remaps the batch,
+    // frame f through the maps of view f % V, into the BGR buffer of the batch's slot; the warp,
+    // the tracker's pyramid, the face / hand crops and the rig's size check read that buffer
+    // (Slot::raw describes it).  n not a multiple of V or another frame size is OPK_ERR_ARG at
+    // submit.  130 frames of 1280x720 are 360 MB per slot; clearing frees both slots' buffers.
+    // Set / clear (nullptr) only with no batch in flight.
+    void set_undistort(const UndistortCameras* cams);
+    bool undistort_set() const { return undist_.views() > 0; }
+    // the collected batch's buffer, valid until the second submit after that batch's (an
+    // OPK_ERR_STATE error without cameras or without a batch collected with them)
+    const FrameSource& undistorted_frames() const;
     // device scratch of the face / hand layers of a batch render (grows, never shrinks)
     void* part_render_scratch(int kind, size_t bytes) { return part_dev_[kind & 1].get(bytes); }
 
@@ -166,6 +179,8 @@ private:
         HeatMap heat{};
         FrameSource raw{};   // a copy of the batch's frame description (submit_frames), for the
                              // face / hand stages; plane[0] NULL: none
+        DevBuf undist;       // the batch's undistorted frames, tight BGR (set_undistort): what raw
+                             // describes then
     };
     struct Part {
         KeypointExtractor* ex = nullptr;
@@ -201,6 +216,9 @@ private:
     DevBuf v3d_dev_;
     HostBuf v3d_host_;
     void check_views(int n, int w, int h) const;   // the OPK_ERR_ARG of a submit against the rig
+    UndistortCameras undist_;         // no views: none
+    FrameSource undist_out_{};        // the collected batch's undistorted frames
+    bool undist_valid_ = false;
     void run_views(const Slot& sl);
     struct NetOutput {
         const float* ptr;
