@@ -1073,6 +1073,75 @@ int opk_undistort_frames(opk_ctx* ctx, const opk_frames_out* dst, const opk_fram
  * without cameras or without a batch collected with them. */
 int opk_pose_set_undistort(opk_pose* pose, const opk_cameras* cams);
 int opk_pose_undistorted_frames(opk_pose* pose, opk_frames* out);
+
+/* ---- Rotated and flipped frames: op::rotateAndFlipFrame (utilities/openCv.cpp:236-282), which
+ * the producer runs on every frame after the undistortion under --frame_rotate / --frame_flip
+ * (producer.cpp:115-126) as a cv::transpose plus cv::flip on the host.
+ *
+ * ROTATED AND FLIPPED FRAMES.  The source S has h rows and w columns; rotate is in degrees, flip 0
+ *   or 1.  r = rotate % 360 (C remainder) must be one of 0, +-90, +-180, +-270; anything else is
+ *   OPK_ERR_ARG with the reference's words, "Rotation angle = R != {0, 90, 180, 270} degrees."
+ *   (R = r).  -270, -180 and -90 mean 90, 180 and 270.  A flip other than 0 or 1 is OPK_ERR_ARG.
+ *   The destination D is h x w for 0 and 180, and w rows x h columns for 90 and 270
+ *   (opk_orient_size).  What rotateAndFlipFrame leaves:
+ *
+ *     rotate   flip 0: D[y][x] =      flip 1: D[y][x] =
+ *        0     S[y][x]                S[y][w-1-x]
+ *       90     S[x][w-1-y]            S[x][y]
+ *      180     S[h-1-y][w-1-x]        S[h-1-y][x]
+ *      270     S[h-1-x][y]            S[h-1-x][w-1-y]
+ *
+ *   (cv::transpose is T[y][x] = S[x][y]; cv::flip 0 mirrors the rows, 1 the columns, -1 both; the
+ *   reference flips the transpose by 0 / none at 90 and by 1 / -1 at 270, the frame itself by
+ *   none / 1 at 0 and by -1 / 0 at 180 -- flip 0 / flip 1 in each pair.  OpenCV is not needed to
+ *   check the table: tests/orient_cases.py restates it as index arithmetic.)
+ *
+ * HOW EACH FORMAT MOVES.  The frames stay in their format; a sample is moved whole.  BGR moves
+ *   pixels of 3 bytes.  NV12 and I420 move the Y plane by the table at (w, h) and the chroma by
+ *   the same table at (w/2, h/2) -- NV12's (U, V) pair is one sample, I420's U and V are two
+ *   planes.  Width and height are even, so 2x2 blocks go to 2x2 blocks: nothing is resampled.
+ *   Hence opk_frames_to_bgr(orient(f)) equals orient(opk_frames_to_bgr(f)) bit for bit.  The same
+ *   is NOT true of opk_bgr_to_frames, whose chroma comes from each block's top-left pixel, which a
+ *   flip or a rotation moves to another corner.
+ *
+ * COORDINATES.  With the pipeline stage set, keypoints come out in the oriented frame's
+ *   coordinates, as in the reference.  opk_orient_keypoints takes [people][parts][3] host arrays
+ *   from source coordinates to oriented ones (inverse 0) or back (inverse 1), in place: the table
+ *   applied to pixel indices -- for (90, 0), oriented (x, y) is source (w-1-y, x) -- each
+ *   coordinate one fp32 subtraction from (float)(w-1) or (float)(h-1), or a copy; width and height
+ *   are the source frame's.  A keypoint whose third value is 0 is left as it is (the reference's
+ *   missing keypoint is (0, 0, 0)).  With inverse 1 a caller puts results back onto the original
+ *   video.  A pure host function, as is opk_orient_size.
+ *
+ * opk_orient_frames: src -> dst, enqueued on the context's stream (kernels/orient.hip, one launch
+ *   per plane).  OPK_ERR_ARG, before any device work: a destination of another format than the
+ *   source, another n, a size other than opk_orient_size's, a source without area, and every
+ *   descriptor error and overlap rule of opk_undistort_frames (in place is refused); n == 0
+ *   succeeds without a launch.  Any row step, frame stride, odd BGR size and base alignment is
+ *   taken: where every base, step and stride of both sides is a multiple of 4 the kernels move
+ *   dwords, otherwise bytes. */
+int opk_orient_size(int width, int height, int rotate, int* out_w, int* out_h);
+int opk_orient_frames(opk_ctx* ctx, const opk_frames_out* dst, const opk_frames* src, int rotate,
+                      int flip);
+int opk_orient_keypoints(float* keypoints_host, int people, int parts, int width, int height,
+                         int rotate, int flip, int inverse);
+/* The orientation as a stage of the raw-frame pipeline, under the attach rules of
+ * opk_pose_set_undistort: setting or clearing with batches in flight is OPK_ERR_STATE; (0, 0)
+ * clears the stage and frees both slots' buffers, and nothing is allocated or launched for it.
+ * While set, opk_pose_submit_frames orients the batch -- after the undistortion when cameras are
+ * set too (the reference's order), reading that stage's BGR buffer -- into a buffer the batch's
+ * slot owns: the source's format, tight rows, grown on demand (one more buffer per slot).  The net
+ * input size, the frame warp, the tracker's pyramid, the face / hand crops and the rig's size check
+ * take the oriented frames and size; the cameras of opk_pose_set_undistort are checked against the
+ * source size.  With a rig set (opk_pose_set_views) its image sizes must therefore be the oriented
+ * ones -- at 90 degrees a rig of the source size is OPK_ERR_ARG at submit -- and supplying camera
+ * matrices of the oriented images is the caller's job: nothing here rotates a camera matrix.
+ * opk_pose_oriented_frames: the description of the collected batch's oriented buffer, under the
+ * lifetime rule of opk_pose_undistorted_frames, for the renders; OPK_ERR_STATE without the stage or
+ * without a batch collected with it.  opk_pose_undistorted_frames keeps returning the undistorted
+ * buffer, which is not rotated. */
+int opk_pose_set_orientation(opk_pose* pose, int rotate, int flip);
+int opk_pose_oriented_frames(opk_pose* pose, opk_frames* out);
 /* The calibration files: <dir>/<serial>.xml as the reference's writer emits them
  * (models/cameraParameters/flir/17012332.xml.example) -- an <opencv_storage> element whose children
  * CameraMatrix (3x4, the extrinsics), Intrinsics (3x3), Distortion (N x 1 or 1 x N, N in {4, 5, 8,

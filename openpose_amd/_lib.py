@@ -200,6 +200,12 @@ _SIGS = {
     "opk_pose_set_undistort": (_i, [_p, _p]),
     "opk_pose_undistorted_frames": (_i, [_p, _p]),
     "opk_camera_parameters_read": (_i, [_c.c_char_p, _c.POINTER(_c.c_char_p), _i, _p, _i, _ip]),
+    # rotated and flipped frames
+    "opk_orient_size": (_i, [_i, _i, _i, _ip, _ip]),
+    "opk_orient_frames": (_i, [_p, _p, _p, _i, _i]),
+    "opk_orient_keypoints": (_i, [_p, _i, _i, _i, _i, _i, _i, _i]),
+    "opk_pose_set_orientation": (_i, [_p, _i, _i]),
+    "opk_pose_oriented_frames": (_i, [_p, _p]),
 }
 
 

@@ -340,6 +340,27 @@ class Context:
         check(self.L.opk_undistort_frames(self.h, ctypes.byref(d), ctypes.byref(s), ctypes.byref(c)))
         return out
 
+    def orient_frames(self, frames, rotate=0, flip=False, out=None):
+        """opk_orient_frames: the frames -- uint8 [n, h, w, 3] (CUDA) or a Frames (BGR, NV12, I420)
+        -- rotated by `rotate` degrees (0, +-90, +-180, +-270) and mirrored if `flip`, as the
+        reference's --frame_rotate / --frame_flip leave them, in their own format: a tensor
+        [n, oh, ow, 3] for a tensor, a Frames for a Frames (or into `out`: such a tensor,
+        [n, oh, row bytes], or a Frames of the format).  (ow, oh) = orient_size((w, h), rotate)."""
+        src = _as_frames(frames)
+        ow, oh = orient_size((src.width, src.height), rotate)
+        if out is None:
+            if isinstance(frames, Frames) and src.format != FRAMES_BGR:
+                out = Frames.empty(src.format, src.n, oh, ow, src.device)
+            else:
+                out = torch.empty((src.n, oh, ow, 3), dtype=torch.uint8, device=src.device)
+                if isinstance(frames, Frames):
+                    out = Frames.bgr(out)
+        dst = out if isinstance(out, Frames) else Frames.bgr(out, ow)
+        s, d = src.struct(), dst.struct_out()
+        check(self.L.opk_orient_frames(self.h, ctypes.byref(d), ctypes.byref(s), int(rotate),
+                                       int(flip)))
+        return out
+
     # ---- person ids across frames -------------------------------------------------------------
     def pyramid(self, frames, levels=3):
         """opk_pyramid_build: the grey image and Gaussian pyramid (`levels` 1..3) of every frame --
@@ -589,6 +610,26 @@ class Context:
             nms_th, scale, int(maximize_positives), semantics))
         k = min(n.value, max_people)
         return kp[:k].copy(), ks[:k].copy()
+
+
+def orient_size(size, rotate):
+    """opk_orient_size: (width, height) of frames of `size` rotated by `rotate` degrees."""
+    w, h = ctypes.c_int(), ctypes.c_int()
+    check(_lib.load().opk_orient_size(int(size[0]), int(size[1]), int(rotate), ctypes.byref(w),
+                                      ctypes.byref(h)))
+    return w.value, h.value
+
+
+def orient_keypoints(keypoints, size, rotate, flip, inverse=False):
+    """opk_orient_keypoints: a copy of keypoints [people, parts, 3] taken from the coordinates of
+    the source frames (`size`, their (width, height)) to those of the oriented frames, or back with
+    `inverse`; points whose third value is 0 stay as they are."""
+    kp = np.array(keypoints, dtype=np.float32, order="C")
+    assert kp.ndim == 3 and kp.shape[2] == 3
+    check(_lib.load().opk_orient_keypoints(kp.ctypes.data_as(ctypes.c_void_p), kp.shape[0],
+                                           kp.shape[1], int(size[0]), int(size[1]), int(rotate),
+                                           int(flip), int(inverse)))
+    return kp
 
 
 def scale_and_size(input_size, net_resolution=(-1, 368), dynamic_behavior=1.0, scale_number=1,
@@ -1355,6 +1396,33 @@ class PoseExtractor:
         t = torch.as_tensor(_DeviceBytes(int(f.plane[0]), (f.n, f.height, f.width * 3),
                                          (frame, step, 1)), device="cuda")
         return Frames.bgr(t, f.width)
+
+    # ---- orientation (opk_pose_set_orientation) ------------------------------------------------
+    def set_orientation(self, rotate=0, flip=False):
+        """--frame_rotate / --frame_flip: from now on submit_frames / forward_frames rotate and
+        mirror the batch (after the undistortion, if set) into a buffer of the batch's slot, in the
+        frames' own format, and every later stage reads that: keypoints come out in the oriented
+        frame's coordinates (orient_keypoints(..., inverse=True) takes them back), and a rig set
+        with set_views must be one of the oriented images.  (0, False) clears and frees the slots'
+        buffers.  Not with batches in flight."""
+        check(self.L.opk_pose_set_orientation(self.h, int(rotate), int(flip)))
+
+    def oriented_frames(self):
+        """The collected batch's oriented frames as a Frames over the pipeline's buffer (no copy):
+        valid until the second submit after that batch's or set_orientation(0, False)."""
+        f = _lib.FramesStruct()
+        check(self.L.opk_pose_oriented_frames(self.h, ctypes.byref(f)))
+
+        def plane(i, rows, row_bytes):
+            return torch.as_tensor(_DeviceBytes(int(f.plane[i]), (f.n, rows, row_bytes),
+                                                (int(f.frame_bytes[i]), int(f.step[i]), 1)),
+                                   device="cuda")
+        w, h = f.width, f.height
+        if f.format == FRAMES_BGR:
+            return Frames.bgr(plane(0, h, w * 3), w)
+        if f.format == FRAMES_NV12:
+            return Frames.nv12(plane(0, h, w), plane(1, h // 2, w), w)
+        return Frames.i420(plane(0, h, w), plane(1, h // 2, w // 2), plane(2, h // 2, w // 2), w)
 
     def person_ids(self, frame):
         """int64 [people] ids of a collected frame, person order of keypoints() (needs a tracker)."""

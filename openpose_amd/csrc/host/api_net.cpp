@@ -1186,6 +1186,33 @@ int opk_pose_undistorted_frames(opk_pose* p, opk_frames* out)
     });
 }
 
+int opk_pose_set_orientation(opk_pose* p, int rotate, int flip)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p, "NULL pose");
+        p->pose->set_orientation(opk::make_orientation(rotate, flip));
+    });
+}
+
+int opk_pose_oriented_frames(opk_pose* p, opk_frames* out)
+{
+    return guarded_net([&] {
+        OPK_CHECK_ARG(p && out, "NULL argument");
+        const opk::FrameSource& f = p->pose->oriented_frames();
+        *out = opk_frames{};
+        out->format = f.format;
+        out->n = f.n;
+        out->width = f.w;
+        out->height = f.h;
+        const int planes = f.format == OPK_FRAMES_BGR ? 1 : f.format == OPK_FRAMES_NV12 ? 2 : 3;
+        for (int i = 0; i < planes; ++i) {
+            out->plane[i] = f.plane[i];
+            out->step[i] = i == 0 ? f.step : f.cstep;
+            out->frame_bytes[i] = f.frame[i];
+        }
+    });
+}
+
 int opk_pose_read_track_times(opk_pose* p, int* batches, double* pyramid_ms, double* lk_ms,
                               double* host_ms)
 {

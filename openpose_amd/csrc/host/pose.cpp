@@ -346,6 +346,56 @@ void PoseHip::set_undistort(const UndistortCameras* cams)
         for (Slot& sl : slots_) sl.undist.release();
 }
 
+void PoseHip::set_orientation(const Orientation& o)
+{
+    if (count_ != 0) throw Error(3, "batches in flight: collect them before setting the orientation");
+    orient_ = o;
+    orient_valid_ = false;
+    orient_out_ = FrameSource{};
+    if (!o.set())   // cleared: the slots' buffers go back
+        for (Slot& sl : slots_) sl.orient.release();
+}
+
+const FrameSource& PoseHip::oriented_frames() const
+{
+    if (!orientation_set()) throw Error(3, "no orientation set");
+    if (!orient_valid_) throw Error(3, "no collected batch with oriented frames");
+    return orient_out_;
+}
+
+namespace {
+// n frames of w x h pixels in `format` with tight rows, plane after plane in `buf`
+FrameDest tight_frames(DevBuf& buf, int format, int n, int w, int h)
+{
+    FrameDest d{};
+    d.format = format;
+    d.n = n;
+    d.w = w;
+    d.h = h;
+    const size_t W = (size_t)w, H = (size_t)h, N = (size_t)n;
+    if (format == kFramesBgr) {
+        d.step = W * 3;
+        d.frame[0] = d.step * H;
+        d.plane[0] = static_cast<uint8_t*>(buf.get(d.frame[0] * N));
+        return d;
+    }
+    const bool nv12 = format == kFramesNv12;
+    d.step = W;
+    d.cstep = nv12 ? W : W / 2;
+    d.cpix = nv12 ? 2 : 1;
+    d.frame[0] = W * H;
+    d.frame[1] = d.frame[2] = d.cstep * (H / 2);
+    // the planes start on 16-byte boundaries of the buffer
+    auto pad16 = [](size_t b) { return (b + 15) / 16 * 16; };
+    const size_t luma = pad16(d.frame[0] * N), chroma = pad16(d.frame[1] * N);
+    uint8_t* base = static_cast<uint8_t*>(buf.get(luma + (nv12 ? chroma : 2 * chroma)));
+    d.plane[0] = base;
+    d.plane[1] = base + luma;
+    d.plane[2] = nv12 ? d.plane[1] + 1 : d.plane[1] + chroma;
+    return d;
+}
+}  // namespace
+
 const FrameSource& PoseHip::undistorted_frames() const
 {
     if (!undistort_set()) throw Error(3, "no cameras set");
@@ -603,18 +653,24 @@ void PoseHip::set_input(int net_w, int net_h, float dyn, int scale_number, doubl
 
 void PoseHip::submit_frames(const FrameSource& decoded)
 {
-    const int n = decoded.n, w = decoded.w, h = decoded.h;
+    const int n = decoded.n;
+    int w = decoded.w, h = decoded.h;
     OPK_CHECK_ARG(net_ != nullptr, "no network: raw frames need the net");
     OPK_CHECK_ARG(decoded.plane[0] != nullptr && n > 0 && w > 0 && h > 0, "empty frames");
     OPK_CHECK_ARG(count_ < 2, "two batches already in flight: collect first");
     OPK_CHECK_ARG(model_ != 6, "BODY_19N (DenseNet normalisation) is not supported");
-    check_views(n, w, h);
+    // every check before any device work: the rig's against the oriented size, the cameras'
+    // against the source's
+    const bool turned = orientation_set() && orient_.turn();
+    check_views(n, turned ? h : w, turned ? w : h);
+    if (undistort_set()) check_cameras(undist_, n, w, h);
+    if (undistort_set() || orientation_set()) check_frames(decoded);
     FrameSource frames = decoded;
+    FrameSource und{}, ori{};
+    Slot& stage_slot = slots_[(head_ + count_) & 1];
     if (undistort_set()) {
         // the first stage: the batch undistorted into its slot's BGR buffer, which every later
         // stage reads in place of the decoder's frames
-        check_cameras(undist_, n, w, h);
-        check_frames(decoded);
         ctx_->bind();
         FrameDest d{};
         d.format = kFramesBgr;
@@ -623,7 +679,7 @@ void PoseHip::submit_frames(const FrameSource& decoded)
         d.h = h;
         d.step = (size_t)w * 3;
         d.frame[0] = d.step * h;
-        d.plane[0] = static_cast<uint8_t*>(slots_[(head_ + count_) & 1].undist.get(d.frame[0] * n));
+        d.plane[0] = static_cast<uint8_t*>(stage_slot.undist.get(d.frame[0] * n));
         undistort_frames(ctx_, d, decoded, undist_, ctx_->stream);
         frames = FrameSource{};
         frames.format = kFramesBgr;
@@ -633,6 +689,29 @@ void PoseHip::submit_frames(const FrameSource& decoded)
         frames.plane[0] = d.plane[0];
         frames.step = d.step;
         frames.frame[0] = d.frame[0];
+        und = frames;
+    }
+    if (orientation_set()) {
+        // the second stage (the reference's order): the batch, undistorted or as decoded, permuted
+        // into its slot's buffer of the same format with tight rows; from here on w x h is the
+        // oriented size
+        ctx_->bind();
+        const FrameDest d = tight_frames(stage_slot.orient, frames.format, n, turned ? h : w,
+                                         turned ? w : h);
+        orient_frames(ctx_, d, frames, orient_, ctx_->stream);
+        frames = FrameSource{};
+        frames.format = d.format;
+        frames.n = n;
+        frames.w = w = d.w;
+        frames.h = h = d.h;
+        for (int i = 0; i < 3; ++i) {
+            frames.plane[i] = d.plane[i];
+            frames.frame[i] = d.frame[i];
+        }
+        frames.step = d.step;
+        frames.cstep = d.cstep;
+        frames.cpix = d.cpix;
+        ori = frames;
     }
     double scales[kMaxResizeSources];
     scale_and_size(w, h, in_net_w_, in_net_h_, dyn_, scale_number_, scale_gap_, scales, input_hw_);
@@ -654,6 +733,8 @@ void PoseHip::submit_frames(const FrameSource& decoded)
     for (int i = 0; i < scale_number_; ++i) map_ratios_[i] = (float)scales[i];
     have_ratios_ = true;
     cur_raw_ = frames;   // a copy, kept in the batch's slot (submit_outputs)
+    cur_und_ = und;
+    cur_ori_ = ori;
     try {
         // the batch's pyramid, into the slot submit_outputs is about to fill, ahead of its nets
         if (tracker_attached()) tracker_->build((head_ + count_) & 1, frames, ctx_->stream);
@@ -663,11 +744,11 @@ void PoseHip::submit_frames(const FrameSource& decoded)
             submit_multi(ptrs, hw, scale_number_, n, w, h);
     } catch (...) {
         have_ratios_ = false;
-        cur_raw_ = FrameSource{};
+        cur_raw_ = cur_und_ = cur_ori_ = FrameSource{};
         throw;
     }
     have_ratios_ = false;
-    cur_raw_ = FrameSource{};
+    cur_raw_ = cur_und_ = cur_ori_ = FrameSource{};
 }
 
 void PoseHip::forward_frames(const FrameSource& frames)
@@ -844,6 +925,8 @@ void PoseHip::submit_outputs(const NetOutput* outs, int nscales, int n, int net_
     sl.scale = scale;
     sl.heat = heat;
     sl.raw = cur_raw_;
+    sl.und = cur_und_;
+    sl.ori = cur_ori_;
     ++count_;
 }
 
@@ -995,8 +1078,11 @@ int PoseHip::collect()
     scale_net_to_output_ = sl.scale;
     heat_valid_ = false;
     // the undistorted frames of this batch: its slot's buffer (submit_frames)
-    undist_valid_ = undistort_set() && sl.raw.plane[0] != nullptr && sl.raw.plane[0] == sl.undist.ptr;
-    undist_out_ = undist_valid_ ? sl.raw : FrameSource{};
+    undist_valid_ = undistort_set() && sl.und.plane[0] != nullptr && sl.und.plane[0] == sl.undist.ptr;
+    undist_out_ = undist_valid_ ? sl.und : FrameSource{};
+    // likewise its oriented frames
+    orient_valid_ = orientation_set() && sl.ori.plane[0] != nullptr && sl.ori.plane[0] == sl.orient.ptr;
+    orient_out_ = orient_valid_ ? sl.ori : FrameSource{};
     run_parts(sl);   // the attached face / hand extractors, on this batch's frames
     run_views(sl);   // the rig: 3-D arrays of this batch's time steps
     run_tracker(sl, si);   // the attached tracker: LK and matching of this batch's frames

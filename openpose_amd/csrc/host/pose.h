@@ -10,6 +10,7 @@
 #include "pool.h"
 #include "track.h"
 #include "triangulate.h"
+#include "orient.h"
 #include "undistort.h"
 
 namespace opk {
@@ -159,6 +160,18 @@ public:
     // the collected batch's buffer, valid until the second submit after that batch's (an
     // OPK_ERR_STATE error without cameras or without a batch collected with them)
     const FrameSource& undistorted_frames() const;
+    // Orientation (the reference's --frame_rotate / --frame_flip, which its producer applies right
+    // after the undistortion): while one is set, submit_frames permutes the batch -- the
+    // undistorted buffer when cameras are set too -- into a buffer of the batch's slot, in the
+    // source's format with tight rows; scale_and_size, the warp, the tracker's pyramid, the face /
+    // hand crops and the rig's size check take the oriented description and size, the cameras'
+    // check the source size.  (0, false) clears the stage and frees both slots' buffers.  Set /
+    // clear only with no batch in flight.
+    void set_orientation(const Orientation& o);
+    bool orientation_set() const { return orient_.set(); }
+    // the collected batch's oriented buffer, under undistorted_frames()' lifetime rule (an
+    // OPK_ERR_STATE error without the stage or without a batch collected with it)
+    const FrameSource& oriented_frames() const;
     // device scratch of the face / hand layers of a batch render (grows, never shrinks)
     void* part_render_scratch(int kind, size_t bytes) { return part_dev_[kind & 1].get(bytes); }
 
@@ -181,6 +194,8 @@ private:
                              // face / hand stages; plane[0] NULL: none
         DevBuf undist;       // the batch's undistorted frames, tight BGR (set_undistort): what raw
                              // describes then
+        DevBuf orient;       // the batch's oriented frames (set_orientation): what raw describes then
+        FrameSource und{}, ori{};   // what undist / orient hold of this batch; plane[0] NULL: nothing
     };
     struct Part {
         KeypointExtractor* ex = nullptr;
@@ -196,6 +211,7 @@ private:
     std::vector<int> part_first_;     // [n + 1]: first person of each frame in the batch's arrays
     bool parts_valid_ = false;
     FrameSource cur_raw_{};           // set by submit_frames for the submit it makes
+    FrameSource cur_und_{}, cur_ori_{};   // likewise: the stages' buffers of that batch
     bool any_attached() const { return attached(0) || attached(1); }
     void need_frames() const;         // the OPK_ERR_STATE of a submit without frames
     void run_parts(const Slot& sl);
@@ -219,6 +235,9 @@ private:
     UndistortCameras undist_;         // no views: none
     FrameSource undist_out_{};        // the collected batch's undistorted frames
     bool undist_valid_ = false;
+    Orientation orient_{};            // not set(): none
+    FrameSource orient_out_{};        // the collected batch's oriented frames
+    bool orient_valid_ = false;
     void run_views(const Slot& sl);
     struct NetOutput {
         const float* ptr;

@@ -108,6 +108,24 @@ void launch_frames_to_bgr(uint8_t* dst, size_t dst_step, const FrameSource& src,
 // dst NV12 / I420 (only the samples are written) from the BGR frames src of the same n, w, h
 void launch_bgr_to_frames(const FrameDest& dst, const FrameSource& src, hipStream_t stream);
 
+// ---- rotated and flipped frames (orient.hip; the definition: include/opk.h) ---------------------
+// One plane of a batch as orient.hip's kernels take it: samples of 1, 2 or 3 bytes, the source
+// plane w samples x h rows, mx / my the mirror of the source's x / y axis.
+struct OrientPlane {
+    const uint8_t* src;
+    uint8_t* dst;
+    size_t sstep, sframe, dstep, dframe;
+    int w, h;
+    int mx, my;
+};
+// dst (src's format and n; src.h x src.w pixels when `turn`) = every plane of src permuted:
+// D[y][x] = S[sy][sx] with (sx, sy) = (x, y), or (y, x) when `turn`, then mirrored on the source's
+// axes by mx / my.  One launch per plane (1 BGR, 2 NV12, 3 I420).
+void launch_orient_frames(const FrameDest& dst, const FrameSource& src, bool turn, bool mx, bool my,
+                          hipStream_t stream);
+// whether launch_orient_frames takes the dword kernels for these frames (else the plain one)
+bool orient_tiled(const FrameDest& dst, const FrameSource& src);
+
 // ---- frame -> net input (input.hip; YUV sources: yuv.hip) ----------------------------------------
 // src: the frames (BGR, or YUV converted on the way: bit for bit the warp of the converted frames);
 // dst [n][3][dh][dw] fp32, n output images.
