@@ -1402,6 +1402,93 @@ int opk_pose_render_frames_to(opk_pose* pose, const opk_frames_out* dst, const o
                               float alpha_keypoint, float alpha_heatmap, int googly_eyes,
                               int blend_original, int cast, const float* part_params);
 
+/* ---- Frames to JPEG files: what op::ImageSaver leaves under --write_images_format jpg and, frame
+ * by frame, under --write_video (saveImage -> cv::imwrite with the default parameters of
+ * filestream/fileStream.hpp:54-57, quality 100; videoSaver.cpp:110-121).  cv::imwrite drives
+ * libjpeg(-turbo) with its defaults: JFIF, YCbCr 4:2:0, JDCT_ISLOW, the standard Huffman tables,
+ * force_baseline.  The bar is equality of files with that library, not PSNR.
+ *
+ * JPEG FRAMES.  One file per frame of w x h pixels (each in 1..65535) at quality q in 1..100.
+ *
+ *   FILE LAYOUT (multi-byte fields big-endian): FFD8; APP0 of length 16 -- "JFIF\0", version 1.01,
+ *   units 0, density 1 x 1, no thumbnail; DQT id 0 (luma) and DQT id 1 (chroma), 64 bytes each in
+ *   zigzag order, 8-bit; SOF0 -- precision 8, height, width, 3 components (1, 0x22, 0), (2, 0x11, 1),
+ *   (3, 0x11, 1); DHT class 0 id 0, class 1 id 0, class 0 id 1, class 1 id 1 (T.81 Annex K.3, K.5,
+ *   K.4, K.6); SOS -- 3 components (1, 0x00), (2, 0x11), (3, 0x11), then 0, 63, 0; the
+ *   entropy-coded data; FFD9.  No restart markers, no comments.  The header is 623 bytes for every
+ *   size and quality.  The tables are constants (kernels/jpeg_tables.inc).
+ *
+ *   QUALITY (jpeg_quality_scaling): s = 5000 / q for q < 50, else 200 - 2q; Q[k] = clamp((base[k] * s
+ *   + 50) / 100, 1, 255) with base the Annex K.1 (luma) and K.2 (chroma) tables.  q = 100 gives all
+ *   ones: the reference's default.
+ *
+ *   COLOUR, int32 with an arithmetic >>, on the R, G, B of a BGR pixel:
+ *     Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *     Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *     Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ *
+ *   EDGES.  The full-resolution planes are padded by replication to the width 16 * ceil(w / 16) and
+ *   to an even height.  Chroma is then downsampled 2 x 2 as (a + b + c + d + bias) >> 2, bias 1 in
+ *   even output columns and 2 in odd ones, and after that its last real row, row ceil(h / 2) - 1,
+ *   is replicated downwards; the last luma row is replicated downwards.  (So below an even height
+ *   that is no multiple of 16 the chroma repeats the mean of the last two rows, the luma the last
+ *   row alone.)
+ *
+ *   BLOCKS.  A component has ceil(w_c / 8) x ceil(h_c / 8) real blocks.  An MCU is Y(0,0), Y(0,1),
+ *   Y(1,0), Y(1,1), Cb, Cr (row, column), MCUs row by row.  A luma block of an MCU outside the real
+ *   blocks (a dummy block) is not transformed: its ACs are 0 and its DC is the quantised DC of the
+ *   block before it in that MCU.  An MCU's chroma blocks are always real.
+ *
+ *   FDCT (jfdctint.c, CONST_BITS 13, PASS1_BITS 2) on samples - 128, rows first, then columns, with
+ *   DESCALE(x, n) = (x + (1 << (n - 1))) >> n and FIX(c) = round(c * 8192).  One pass over d0..d7:
+ *     t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5,
+ *     t3 = d3 + d4, t4 = d3 - d4;  t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2
+ *     rows:    o0 = (t10 + t11) << 2,        o4 = (t10 - t11) << 2,        n = 11
+ *     columns: o0 = DESCALE(t10 + t11, 2),   o4 = DESCALE(t10 - t11, 2),   n = 15
+ *     z1 = (t12 + t13) FIX(0.541196100)
+ *     o2 = DESCALE(z1 + t13 FIX(0.765366865), n),  o6 = DESCALE(z1 - t12 FIX(1.847759065), n)
+ *     z1 = t4 + t7, z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7, z5 = (z3 + z4) FIX(1.175875602)
+ *     t4 *= FIX(0.298631336), t5 *= FIX(2.053119869), t6 *= FIX(3.072711026), t7 *= FIX(1.501321110)
+ *     z1 *= -FIX(0.899976223), z2 *= -FIX(2.562915447),
+ *     z3 = -z3 FIX(1.961570560) + z5, z4 = -z4 FIX(0.390180644) + z5
+ *     o7 = DESCALE(t4 + z1 + z3, n), o5 = DESCALE(t5 + z2 + z4, n),
+ *     o3 = DESCALE(t6 + z2 + z3, n), o1 = DESCALE(t7 + z1 + z4, n)
+ *   Every intermediate fits int32.
+ *
+ *   QUANTISATION.  With qv = 8 Q in natural order, c = sign(f) * ((|f| + (qv >> 1)) / qv); the block
+ *   is then read in zigzag order.
+ *
+ *   ENTROPY CODING.  The DC difference is taken against the previous block of the same component
+ *   in stream order, dummy blocks included, from 0 at the start of a frame.  A value v has size
+ *   n = bit_length(|v|); its n extra bits are v for v >= 0, else the low n bits of v - 1.  An AC is
+ *   coded as the symbol (run << 4 | n), after one ZRL (0xF0) for each full run of 16 zeros before
+ *   it; EOB (0x00) follows when the block ends in zeros.  Bits go MSB first, the last byte is
+ *   filled with 1-bits, and a 0x00 follows every 0xFF data byte, a last byte made 0xFF by the fill
+ *   included.
+ *
+ *   OTHER FORMATS.  An NV12 or I420 source gives the file of opk_frames_to_bgr(frames): JFIF is
+ *   full range and these formats are limited range, so nothing is taken from the planes directly.
+ *
+ * opk_jpeg_bound: a capacity that n frames of w x h can never exceed (derived in host/jpeg.cpp:
+ *   1660 bits per block at most, doubled by stuffing, plus 625 bytes); 0 for nothing to encode.
+ * opk_jpeg_encode_host: the plain C++ encoder of n host BGR frames (step, frame_bytes: 0 = tight);
+ *   needs no context and no device.
+ * opk_jpeg_encode: the same files from device frames, enqueued on the context's stream
+ *   (kernels/jpeg.hip).  Frame f's file is dst[offsets[f] .. offsets[f + 1]): the files are packed,
+ *   offsets[0] = 0, offsets has n + 1 entries.  A frame whose end would pass `capacity` is not
+ *   written at all, nor is any frame after it; the offsets are still the true ones, so
+ *   offsets[n] > capacity tells how much room the batch needs.  No byte at or past dst + capacity
+ *   is touched.  The files do not depend on the order in which workgroups arrive: they are the same
+ *   from run to run and the same as the host route's.
+ * OPK_ERR_ARG, before any work: every descriptor error of opk_frames, a width or height outside
+ *   1..65535, a quality outside 1..100, a NULL dst or offsets with n > 0, dst overlapping the
+ *   source.  n == 0 succeeds: offsets[0] = 0 on the host route, no launch on the device route. */
+size_t opk_jpeg_bound(int n, int w, int h);
+int opk_jpeg_encode_host(uint8_t* dst, size_t capacity, uint64_t* offsets, const uint8_t* bgr,
+                         size_t step, size_t frame_bytes, int n, int w, int h, int quality);
+int opk_jpeg_encode(opk_ctx* ctx, uint8_t* dst_dev, size_t capacity, uint64_t* offsets_dev,
+                    const opk_frames* frames, int quality);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,10 @@ _SIGS = {
     "opk_orient_keypoints": (_i, [_p, _i, _i, _i, _i, _i, _i, _i]),
     "opk_pose_set_orientation": (_i, [_p, _i, _i]),
     "opk_pose_oriented_frames": (_i, [_p, _p]),
+    # frames to JPEG files
+    "opk_jpeg_bound": (_c.c_size_t, [_i, _i, _i]),
+    "opk_jpeg_encode_host": (_i, [_p, _c.c_size_t, _p, _p, _c.c_size_t, _c.c_size_t, _i, _i, _i, _i]),
+    "opk_jpeg_encode": (_i, [_p, _p, _c.c_size_t, _p, _p, _i]),
 }
 
 

@@ -230,6 +230,76 @@ def _as_frames(frames, width=None, rows=False):
     return Frames.bgr(frames, width)
 
 
+def jpeg_bound(n, width, height):
+    """opk_jpeg_bound: a capacity that n JPEG files of width x height frames never exceed."""
+    return int(_lib.load().opk_jpeg_bound(int(n), int(width), int(height)))
+
+
+class JpegBatch:
+    """The files of Context.encode_jpeg: frame f's file is data[offsets[f] : offsets[f + 1]].
+    `data` (uint8 CUDA tensor, or numpy under host_only) stays on its side until asked for:
+    .offsets (numpy uint64 [n + 1], one small download that waits for the encoder) and .sizes come
+    first, .bytes(f) downloads one file, .tobytes_list() the batch in one copy."""
+
+    def __init__(self, ctx, n, width, height, data, capacity, offsets_buf, host, source=None):
+        self.ctx, self.n, self.width, self.height = ctx, n, width, height
+        self.data, self.capacity, self.host = data, capacity, host
+        self._offsets_buf, self._offsets = offsets_buf, None
+        self._source = source   # the frames stay alive until the encoder has run
+
+    @property
+    def offsets(self):
+        if self._offsets is None:
+            if self.host:
+                o = self._offsets_buf[:self.n + 1].copy()
+            elif self.n == 0:
+                o = np.zeros(1, np.uint64)   # no launch: nothing was written
+            else:
+                self.ctx.sync()
+                o = self._offsets_buf[:self.n + 1].cpu().numpy().view(np.uint64)
+            self._source = None
+            if int(o[-1]) > self.capacity:
+                raise OpkError("encode_jpeg: the files need %d bytes, the buffer holds %d"
+                               % (int(o[-1]), self.capacity))
+            self._offsets = o
+        return self._offsets
+
+    @property
+    def sizes(self):
+        return np.diff(self.offsets)
+
+    def _download(self, lo, hi):
+        part = self.data[lo:hi]
+        return part.tobytes() if self.host else part.cpu().numpy().tobytes()
+
+    def bytes(self, f):
+        o = self.offsets
+        return self._download(int(o[f]), int(o[f + 1]))
+
+    def tobytes_list(self):
+        o = self.offsets
+        blob = self._download(0, int(o[-1]))
+        return [blob[int(o[f]):int(o[f + 1])] for f in range(self.n)]
+
+    def save(self, directory, names=None, first_index=None):
+        """<directory>/<name>_rendered.jpg for each frame, as op::ImageSaver::saveImages names them;
+        with first_index=k instead %012d_rendered.jpg from k on, op::VideoSaver's temporary frames.
+        Returns the paths."""
+        if (names is None) == (first_index is None):
+            raise ValueError("names or first_index")
+        if names is None:
+            names = ["%012d" % (first_index + f) for f in range(self.n)]
+        if len(names) != self.n:
+            raise ValueError("%d names for %d frames" % (len(names), self.n))
+        os.makedirs(directory, exist_ok=True)
+        paths = []
+        for name, blob in zip(names, self.tobytes_list()):
+            paths.append(os.path.join(directory, "%s_rendered.jpg" % name))
+            with open(paths[-1], "wb") as fh:
+                fh.write(blob)
+        return paths
+
+
 # Handles still open at interpreter exit (e.g. held by a test traceback) are closed before the HIP
 # runtime's own teardown: poses, then nets, then contexts.
 _LIVE = {"pose": weakref.WeakSet(), "extractor": weakref.WeakSet(), "tracker": weakref.WeakSet(),
@@ -360,6 +430,56 @@ class Context:
         check(self.L.opk_orient_frames(self.h, ctypes.byref(d), ctypes.byref(s), int(rotate),
                                        int(flip)))
         return out
+
+    # ---- frames to JPEG files --------------------------------------------------------------------
+    def encode_jpeg(self, frames, quality=100, out=None, capacity=None):
+        """opk_jpeg_encode: the frames -- uint8 [n, h, w, 3] (CUDA) or a Frames (BGR, NV12, I420) --
+        as baseline JPEG files, byte for byte what libjpeg writes for cv::imwrite's defaults at
+        `quality` (the reference saves at 100), packed into one device buffer: a JpegBatch.
+        Under host_only() the frames are a numpy uint8 [n, h, w, 3] (rows and frames may be
+        strided) and opk_jpeg_encode_host runs.  The buffer holds jpeg_bound(n, w, h) bytes unless
+        `capacity` says otherwise or `out` -- a JpegBatch of an earlier call, whose buffers are
+        reused -- is given; files that do not fit raise OpkError naming the bytes needed."""
+        host = self.device < 0
+        if host:
+            a = np.asarray(frames)
+            assert a.dtype == np.uint8 and a.ndim == 4 and a.shape[3] == 3, "uint8 [n, h, w, 3]"
+            n, h, w = a.shape[:3]
+            if n and h and w and (a.strides[3] != 1 or a.strides[2] != 3 or a.strides[1] < 3 * w
+                                  or (n > 1 and a.strides[0] <= 0)):
+                a = np.ascontiguousarray(a)
+            src = a
+        else:
+            src = _as_frames(frames)
+            n, h, w = src.n, src.height, src.width
+        if out is not None:
+            assert isinstance(out, JpegBatch) and out.host == host and capacity is None
+            data, cap = out.data, out.capacity
+            offsets = out._offsets_buf if out._offsets_buf.shape[0] >= n + 1 else None
+        else:
+            cap = jpeg_bound(n, w, h) if capacity is None else int(capacity)
+            data, offsets = None, None
+        if host:
+            if data is None:
+                data = np.empty(max(cap, 1), np.uint8)
+            if offsets is None:
+                offsets = np.zeros(n + 1, np.uint64)
+            step, frame = (a.strides[1], a.strides[0]) if n and h and w else (0, 0)
+            check(self.L.opk_jpeg_encode_host(
+                data.ctypes.data_as(ctypes.c_void_p), cap, offsets.ctypes.data_as(ctypes.c_void_p),
+                a.ctypes.data_as(ctypes.c_void_p), step, frame if n > 1 else 0, n, w, h, int(quality)))
+        else:
+            if data is None:
+                data = torch.empty(max(cap, 1), dtype=torch.uint8, device=src.device)
+            if offsets is None:
+                offsets = torch.zeros(n + 1, dtype=torch.int64, device=src.device)
+            s = src.struct()
+            check(self.L.opk_jpeg_encode(self.h, _ptr(data), cap, _ptr(offsets), ctypes.byref(s),
+                                         int(quality)))
+        batch = JpegBatch(self, n, w, h, data, cap, offsets, host, src)
+        if cap < jpeg_bound(n, w, h):
+            batch.offsets   # may not fit: look now
+        return batch
 
     # ---- person ids across frames -------------------------------------------------------------
     def pyramid(self, frames, levels=3):
@@ -1684,6 +1804,23 @@ class PoseExtractor:
             int(element), threshold, alpha, alpha_heatmap, int(googly_eyes), int(blend_original),
             cast))
         return out
+
+    def write_images(self, directory, names, frames, quality=100, **render_args):
+        """--write_images <directory> --write_images_format jpg: the last collected batch drawn on
+        `frames` (render_frames with render_args, into a BGR buffer this object keeps), encoded
+        (Context.encode_jpeg) and saved as <name>_rendered.jpg (JpegBatch.save).  frames as for
+        render_frames, undistorted_frames() and oriented_frames() included.  Returns the paths."""
+        if "out" in render_args or "out_format" in render_args:
+            raise ValueError("write_images draws into its own BGR buffer")
+        src = _as_frames(frames)
+        ow, oh = render_args.get("out_size") or (src.width, src.height)
+        buf = getattr(self, "_write_bgr", None)
+        if buf is None or buf.numel() < src.n * oh * ow * 3 or buf.device != src.device:
+            buf = self._write_bgr = torch.empty(src.n * oh * ow * 3, dtype=torch.uint8,
+                                                device=src.device)
+        drawn = buf[:src.n * oh * ow * 3].view(src.n, oh, ow, 3)
+        self.render_frames(src, out=drawn, **render_args)
+        return self.ctx.encode_jpeg(drawn, quality).save(directory, names)
 
     def set_timing(self, on=True):
         check(self.L.opk_pose_set_timing(self.h, int(on)))

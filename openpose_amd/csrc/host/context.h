@@ -69,6 +69,11 @@ struct Context {
     std::map<std::string, std::unique_ptr<UndistortDev>> undistort_maps;
     const UndistortDev& undistort_dev(const UndistortCameras& cams);
 
+    // JPEG frames (host/jpeg_dev.cpp): the device copy of the JpegTables of the last (w, h, quality)
+    // seen, the scratch of one chunk of frames, and the BGR frames of a chunk of a YUV source
+    DevBuf jpeg_tables, jpeg_scratch, jpeg_bgr;
+    int jpeg_key[3] = {0, 0, 0};
+
     // streams other objects of this context run device work on besides `stream` (PoseHip's
     // post-processing stream, its multi-scale net streams): opk_sync waits for them too
     std::vector<hipStream_t> side_streams;

@@ -126,6 +126,36 @@ void launch_orient_frames(const FrameDest& dst, const FrameSource& src, bool tur
 // whether launch_orient_frames takes the dword kernels for these frames (else the plain one)
 bool orient_tiled(const FrameDest& dst, const FrameSource& src);
 
+// ---- frames to JPEG files (jpeg.hip; the definition: include/opk.h; the arithmetic: jpeg_dev.h) ----
+constexpr int kJpegSegMcus = 8;        // consecutive MCUs whose bits one workgroup of jpeg_write assembles
+constexpr int kJpegPackBytes = 4096;   // bytes of the bit stream per workgroup of jpeg_count_ff / jpeg_pack
+struct JpegTables;
+// One chunk of BGR frames through the seven launches of jpeg.hip.  The scratch (host/jpeg_dev.cpp
+// lays it out) is per frame of the chunk; the offsets and the destination are the whole batch's.
+struct JpegJob {
+    const uint8_t* bgr;            // the chunk's first frame
+    size_t step, frame;            // row bytes, bytes from frame to frame
+    int w, h, frames;              // frames: of this chunk
+    int first;                     // index of the chunk's first frame in the batch
+    int mcus, segs, pieces;        // per frame: MCUs, ceil(mcus / kJpegSegMcus), rawcap / kJpegPackBytes
+    size_t rawcap;                 // bytes of a frame's bit stream scratch: the bound, a multiple of kJpegPackBytes
+    const JpegTables* tab;         // device copy
+    short* coef;                   // [frames][mcus][6][64] quantised, zigzag order
+    unsigned short* blockbits;     // [frames][mcus][6]
+    unsigned* segbits;             // [frames][segs]
+    unsigned long long* segstart;  // [frames][segs + 1] first bit of each segment; the last: all bits
+    uint8_t* raw;                  // [frames][rawcap] the bit stream before stuffing, 16-byte aligned
+    unsigned long long* rawbytes;  // [frames] its bytes, the fill included
+    unsigned* ffcount;             // [frames][pieces] 0xFF bytes of each piece
+    unsigned long long* ffstart;   // [frames][pieces] 0xFF bytes before each piece
+    int* fits;                     // [frames] the file ends inside the capacity
+    uint8_t* dst;
+    size_t capacity;
+    unsigned long long* offsets;   // [batch frames + 1]
+};
+// dwords: every frame base and row step of the chunk is a multiple of 4
+void launch_jpeg_chunk(const JpegJob& job, bool dwords, hipStream_t stream);
+
 // ---- frame -> net input (input.hip; YUV sources: yuv.hip) ----------------------------------------
 // src: the frames (BGR, or YUV converted on the way: bit for bit the warp of the converted frames);
 // dst [n][3][dh][dw] fp32, n output images.
